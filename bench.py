@@ -15,17 +15,26 @@ called from the library: counters all-reduce, point-to-point coverage halos,
 teardown split N ways, all-reduce of the partial results) -> integer results on
 the host.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with the
+Prints ONE JSON line on rank 0 (`metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step`, ...) with the per-kernel times of the timed steps and the
 `roofline` of the dominant kernel (Quality Score: 150 of the 254 algorithmic
-bytes per record), the `cpu_baseline` (the C oracle, 1 core, bounded sample; an
-all-cores figure beside it), and -- at N = 1 -- the two other rates the metric
-is about: `h2d_inclusive` (pinned host SoA batches through ngsq_process_batch)
-and `file_end_to_end` (a synthetic BGZF BAM through `ngs qc` to the JSON), with
-`ingest_roofline` for the device inflate kernel that bounds the latter.
+bytes per record).  A plain run sets up, warms up, times --steps steps once and
+prints the line; --dump-outputs DIR also writes what the last step computed.
+
+--full adds everything else (and times --repeats 3 loops): the dominant kernel's
+HBM traffic measured by rocprofv3 --pmc passes of this command, the card's
+clocks, the full-size invariants (`parity_check`), the other Coverage path, the
+`cpu_baseline` (the C oracle, 1 core, bounded sample; an all-cores figure beside
+it), and -- at N = 1 -- the two other rates the metric is about:
+`h2d_inclusive` (pinned host SoA batches through ngsq_process_batch) and
+`file_end_to_end` (a synthetic BGZF BAM through `ngs qc` to the JSON), with
+`ingest_roofline` for the device inflate kernel that bounds the latter, and the
+mixed, extra-facet, all-facet and whole-genome legs.
 """
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import os
 import subprocess
@@ -46,7 +55,15 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=3, help="timed loops of --steps steps each; `value` is the median loop")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed loops of --steps steps each; `value` is the median loop (default 1, with --full 3)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the profiled traffic passes, the card's clocks, the full-size "
+                         "invariants, the other Coverage path, the CPU baseline and the legs (mixed, h2d, stager, file, extra "
+                         "facets, all facets, whole genome; at N > 1 the sharded file legs).  Off: set up, warm up, time, print")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the arrays the last step computed (the ngsq_get_* results the caller "
+                         "receives) as DIR/<name>.npy, float64")
     ap.add_argument("--records", type=int, default=100_000_000, help="records per GPU")
     ap.add_argument("--read-len", type=int, default=150)
     ap.add_argument("--workload", choices=["fixed", "mixed"], default="fixed")
@@ -99,7 +116,7 @@ def parse_args():
                     help="N = 1: records of the whole_genome leg -- the 195-sequence GRCh38 header at full length, records on all of it (0 = skip)")
     ap.add_argument("--whole-genome-steps", type=int, default=7)
     ap.add_argument("--live-traffic", type=int, default=1,
-                    help="1 (N = 1, default workload): two short passes of this script under rocprofv3 --pmc (FETCH_SIZE, WRITE_SIZE -- "
+                    help="with --full, 1 (N = 1, default workload): two short passes of this script under rocprofv3 --pmc (FETCH_SIZE, WRITE_SIZE -- "
                          "separate passes, child processes started before this one touches HIP) give roofline.traffic of THIS run; "
                          "0, or any failure: the committed profiles/*_traffic.json")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
@@ -144,12 +161,16 @@ def launch_ranks(n: int) -> int:
 
 
 def build_once():
-    """Every rank may be the first to arrive on a fresh checkout: serialise the (usually no-op) build."""
+    """Every rank may be the first to arrive on a fresh checkout: serialise the (usually no-op) build.  The lock is taken on
+    the package directory itself, opened read-only: a checkout built by build() and not writable by this user runs as well."""
     import fcntl
     from ngs_amd import build
-    with open(os.path.join(ROOT, "ngs_amd", ".build.lock"), "w") as lk:
-        fcntl.flock(lk, fcntl.LOCK_EX)
+    fd = os.open(os.path.join(ROOT, "ngs_amd"), os.O_RDONLY | os.O_DIRECTORY)
+    try:
+        fcntl.flock(fd, fcntl.LOCK_EX)
         build.build(verbose=False)
+    finally:
+        os.close(fd)
 
 
 
@@ -264,8 +285,66 @@ def median(xs):
     return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
 
 
+DUMP_MAX_ELEMS = 1 << 18   # per array: a larger one is written as a fixed, seeded sample of its entries (+ <name>_index.npy)
+DUMP_MAX_BYTES = 64 << 20  # in all: the sample size is halved until the files fit
+
+
+def dump_outputs(ctx, ffi, np, facets: int, out_dir: str) -> None:
+    """--dump-outputs DIR: what the last timed step left for its caller -- the arrays of the ngsq_get_* entry points of the
+    facets scanned -- as DIR/<name>.npy in float64 (the u64 counts are exact below 2^53).  The same arguments give the
+    same inputs, so two builds compare output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    if facets & ffi.FACET_GENERAL:
+        g = ctx.general()
+        arrays["general"] = [g[k] for k in ffi.GENERAL_FIELDS]
+        arrays["general_read_one_cigar_ops"] = g["read_one_cigar_ops"]
+        arrays["general_read_two_cigar_ops"] = g["read_two_cigar_ops"]
+    if facets & ffi.FACET_TEMPLATE_LENGTH:
+        h, processed, ignored = ctx.template_length()
+        arrays["template_length_histogram"] = h
+        arrays["template_length_counts"] = [processed, ignored]
+    if facets & ffi.FACET_GC_CONTENT:
+        gc = ctx.gc_content()
+        arrays["gc_content_histogram"] = gc.pop("histogram")
+        arrays["gc_content_counts"] = [gc[k] for k in sorted(gc)]
+    if facets & ffi.FACET_QUALITY_SCORE:
+        arrays["quality_scores"] = ctx.quality_scores()
+    if facets & ffi.FACET_COVERAGE:
+        for r in range(len(ctx._ref_len)):
+            seen, hist, ign, bins = ctx.coverage_sequence(r)
+            if seen:
+                arrays[f"coverage_{r}_depth_histogram"] = hist
+                arrays[f"coverage_{r}_ignored"] = [ign]
+                arrays[f"coverage_{r}_bins"] = bins
+        arrays["coverage_nonsensical"] = [ctx.coverage_nonsensical()]
+    if facets & ffi.FACET_EDITS:
+        r1, r2, vaf = ctx.edits()
+        arrays["edits_read_one"], arrays["edits_read_two"], arrays["edits_vaf_histogram"] = r1, r2, vaf
+        for r in range(len(ctx._ref_len)):
+            refs, alts = ctx.edits_positions(r)
+            arrays[f"edits_{r}_refs_per_position"], arrays[f"edits_{r}_alts_per_position"] = refs, alts
+    if facets & ffi.FACET_FEATURES:
+        f = ctx.features()
+        arrays["features"] = [f[k] for k in ffi.FEATURES_FIELDS]
+    e = ctx.error_counts()
+    arrays["error_counts"] = [e[k] for k in ffi.ERROR_FIELDS]
+    arrays = {name: np.asarray(a) for name, a in arrays.items()}
+    cap = DUMP_MAX_ELEMS
+    while cap > 1 and sum(8 * (a.size if a.size <= cap else 2 * cap) for a in arrays.values()) > DUMP_MAX_BYTES:
+        cap //= 2
+    for name, a in arrays.items():
+        if a.size > cap:   # (sampled before the conversion: no float64 copy of a whole per-position array)
+            idx = np.sort(np.random.default_rng(GC_SEED).choice(a.size, cap, replace=False))
+            np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64))
+
+
 def main() -> int:
     args = parse_args()
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args.gpus)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -285,10 +364,11 @@ def main() -> int:
         return pmc_inflate_child(args, json_fd)
     live = (None, None)
     args.live_inflate = None
-    if world == 1 and args.live_traffic and not args.pmc_child and args.workload == "fixed" and not args.emulate_shard and args.file_records > 0:
+    if (args.full and world == 1 and args.live_traffic and not args.pmc_child and args.workload == "fixed" and not args.emulate_shard
+            and args.file_records > 0):
         args.live_inflate = live_inflate_traffic(args)   # (child processes; nothing in this process has touched HIP yet)
-    if (world == 1 and args.live_traffic and not args.pmc_child and args.workload == "fixed" and not args.emulate_shard and not args.force_dist
-            and (args.facets & 0x08)):
+    if (args.full and world == 1 and args.live_traffic and not args.pmc_child and args.workload == "fixed" and not args.emulate_shard
+            and not args.force_dist and (args.facets & 0x08)):
         live = live_pmc_traffic(args)   # (child processes; nothing in this process has touched HIP yet)
         if args.mixed_records > 0 and args.facets == 0x1F and live[0] is not None:   # (not after a failure: at most one time limit is spent)
             args.live_mixed = live_pmc_traffic(args, mixed=True)
@@ -356,10 +436,13 @@ def main() -> int:
     # the timed region: `repeats` loops of EXACTLY --steps steps, each bracketed by barrier + synchronize; `value` is the median
     # loop (all of them are in the line, with the clocks the card ran at), so that a slow box shows as one
     loops = []
-    pci_buf = __import__("ctypes").create_string_buffer(64)
-    pci = pci_buf.value.decode() if lib.ngsq_device_pci_bus_id(device, pci_buf, 64) > 0 else ""
-    pci = pci_buf.value.decode()
-    with ClockSampler(device, pci) as clocks:
+    clocks = None
+    if args.full:   # the card's clocks, power and temperature while the loops run
+        pci_buf = __import__("ctypes").create_string_buffer(64)
+        pci = pci_buf.value.decode() if lib.ngsq_device_pci_bus_id(device, pci_buf, 64) > 0 else ""
+        pci = pci_buf.value.decode()
+        clocks = ClockSampler(device, pci)
+    with clocks if clocks is not None else contextlib.nullcontext():
         for _ in range(max(1, args.repeats)):
             sync()
             t0 = time.perf_counter()
@@ -372,12 +455,15 @@ def main() -> int:
             loops.append(dt)
     elapsed = median(loops)
     total_records = n * world
-    parity = check_invariants(ctx, ffi, total_records, args, mixed, emu_world > world)
+    if args.dump_outputs and rank == 0:   # (every rank holds the whole-file result)
+        dump_outputs(ctx, ffi, np, args.facets, args.dump_outputs)
+    parity = check_invariants(ctx, ffi, total_records, args, mixed, emu_world > world) if args.full else None
     timing = ctx.kernel_timing()
     # N = 1: the OTHER Coverage path on the same resident records, so that the 1 -> 2 step of the scaling curve (which
     # switches from streaming to the difference arrays: DESIGN.md section 5.4) can be read as communication only
     coverage_paths = None
-    if world == 1 and not args.emulate_shard and (args.facets & ffi.FACET_COVERAGE) and not args.force_dist and not args.pmc_child:
+    if (args.full and world == 1 and not args.emulate_shard and (args.facets & ffi.FACET_COVERAGE) and not args.force_dist
+            and not args.pmc_child):
         other = "array" if args.coverage == "stream" else "stream"
         coverage_paths = {args.coverage: round(elapsed / args.steps * 1e3, 3)}
         try:
@@ -399,7 +485,7 @@ def main() -> int:
         except Exception as e:  # noqa: BLE001 -- reported, never required
             coverage_paths["failed"] = f"{type(e).__name__}: {e}"
 
-    rc = 0 if parity.startswith("ok") else 1
+    rc = 0 if parity is None or parity.startswith("ok") else 1
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = total_records * args.steps / elapsed
@@ -430,7 +516,7 @@ def main() -> int:
             "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
             "ms_per_step_each_loop": [round(t / args.steps * 1e3, 3) for t in loops],
             "loops": "%d timed loops of %d steps each; value and ms_per_step are the median loop's" % (len(loops), args.steps),
-            "gpu_state": clocks.summary(), "higher_is_better": True,
+            "gpu_state": clocks.summary() if clocks is not None else None, "higher_is_better": True, "full": args.full,
             "scaling": "weak", "vs_baseline": None, "dtype": "u8/u32 integer (u64 accumulators)",
             "data": "synthetic",
             "config": {"workload": ("BASELINE configs[2]: %d M synthetic %s reads per GPU resident in HBM, "
@@ -463,7 +549,7 @@ def main() -> int:
     ctx.close()
     comm_kind = comm.kind if comm is not None else None
     shared_file = None
-    if comm is not None and world > 1 and args.file_records > 0 and not mixed and not args.emulate_shard:
+    if args.full and comm is not None and world > 1 and args.file_records > 0 and not mixed and not args.emulate_shard:
         # ---- every rank: ONE BAM file, each rank streaming its BGZF block range of it inside this process (HIP is up, the
         # communicator exists): the streaming rate of N GPUs on one file, without the process starts of `ngs qc --gpus N`
         try:
@@ -475,7 +561,7 @@ def main() -> int:
         comm.destroy()
     if rank == 0:
         # ---- the legs beside the headline number: rank 0 at N = 1 only, each bounded to seconds
-        if world == 1 and not args.emulate_shard and not args.pmc_child:
+        if args.full and world == 1 and not args.emulate_shard and not args.pmc_child:
             if args.cpu_sample > 0:
                 out["cpu_baseline"] = cpu_baseline(lib, host, ffi, scfg, min(args.cpu_sample, n), max_len)
             if args.mixed_records > 0 and not mixed:
@@ -493,7 +579,7 @@ def main() -> int:
                 out["all_facets"] = guarded(leg_all_facets, lib, host, ffi, np, args, device)
             if args.whole_genome_records > 0 and not mixed and args.facets == 0x1F:
                 out["whole_genome"] = guarded(leg_whole_genome, lib, host, ffi, np, args, device)
-        elif world > 1 and args.file_records > 0 and not mixed and not args.emulate_shard:
+        elif args.full and world > 1 and args.file_records > 0 and not mixed and not args.emulate_shard:
             # the number the metric is named after, on N GPUs: ONE BAM file scanned by `ngs qc --gpus N` (the other ranks
             # of this launch have released their devices and are on their way out)
             out["file_end_to_end"] = guarded(leg_file_sharded, lib, host, ffi, args, world, comm_kind, shared_file)
