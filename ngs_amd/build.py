@@ -19,7 +19,7 @@ HEADERS = ["kernels.h", "context.h", "comm.h", "mem_pool.h", "ingest_kernels.h",
            "../../include/ngsq_reference.h", "../../include/ngsq_comm.h",
            "../../include/ngsq_shared.h", "../../include/ngsq_synth.h", "../../include/ngsq_bam.h", "../../include/ngsq_stage.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-result", "-fno-gpu-rdc"]
-FLAGS += os.environ.get("NGSQ_EXTRA_FLAGS", "").split()  # measurement builds, e.g. -DNGSQ_INFLATE_PROFILE (use --force)
+FLAGS += os.environ.get("NGSQ_EXTRA_FLAGS", "").split()  # extra compiler flags for a local build, e.g. -save-temps (use --force)
 OBJ_DIR = os.path.join(HERE, "_obj")  # per-source objects (git-ignored): only changed sources recompile
 
 

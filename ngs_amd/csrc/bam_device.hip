@@ -103,10 +103,7 @@ __device__ __forceinline__ bool bin_fits(int32_t pos, uint32_t bin) {
 }
 
 constexpr uint32_t SUB_NONE = 0xFFFFFFFFu;
-#ifndef NGSQ_PARSE_THREADS
-#define NGSQ_PARSE_THREADS 256
-#endif
-constexpr uint32_t PT = NGSQ_PARSE_THREADS; // threads per block of the fixed-pitch parse kernels
+constexpr uint32_t PT = 256; // threads per block of the fixed-pitch parse kernels
 
 // Walk the chain from `o` until it reaches `end` (segment end) or the record at the cursor is not
 // completely inside [0, n_bytes).  STRICT: apply the plausibility test.  Returns false on an invalid

@@ -182,12 +182,10 @@ struct DeviceIngest {
     // Compressed chunks come from a reader thread: while the GPU inflates and parses chunk k the
     // thread reads and frames chunk k+1 into the other pinned buffer.
     struct HostChunk {
-        uint8_t *h = nullptr; // the chunk's compressed bytes: h[j] = byte file_off + j of the file -- in `pin` (behind a pad that makes
-                              // the address congruent to the file offset mod 4096: O_DIRECT reads land where they belong), or, for a
-                              // chunk whose bytes are in the page cache, in the MAPPING of the file itself (nothing is copied by the host)
+        uint8_t *h = nullptr; // the chunk's compressed bytes: h[j] = byte file_off + j of the file -- in `pin`, behind a pad that makes
+                              // the address congruent to the file offset mod 4096: O_DIRECT reads land where they belong
         uint8_t *pin = nullptr; // pinned block, 2 x comp_chunk + 2 pages (mem_pool.h)
         size_t h_bytes = 0;     // of the block behind pin
-        bool mapped = false;    // h points into the file's mapping
         size_t fill = 0, consumed = 0;
         uint64_t total = 0; // decompressed bytes of `blocks`
         std::vector<BgzfBlock> blocks;
@@ -206,6 +204,7 @@ struct DeviceIngest {
     // bytes inflate 22 % faster per byte in launches twice the size).  Now the inflates of chunks j + 1 and j + 2 are queued
     // while chunk j is parsed: j + 1 on the other stream, so that its decoders take the wave slots chunk j's leave.
     static constexpr int NC = 4, NR = 3;
+    static constexpr uint64_t INFLATE_AHEAD = 2; // inflates queued beyond the chunk being parsed
     // the compressed bytes of a chunk cross PCIe on their own stream as soon as the reader thread has
     // framed them, i.e. while the GPU works on the previous chunk
     DevBuf<uint8_t> d_comp_slot[NC];
@@ -252,10 +251,8 @@ struct DeviceIngest {
     hipEvent_t retired_ev[NC] = {nullptr, nullptr, nullptr, nullptr}, inf_done[NC] = {nullptr, nullptr, nullptr, nullptr};
     bool retired_set[NC] = {false, false, false, false}; // (under mu)
     uint64_t chunks_issued = 0, chunks_loaded = 0; // inflates queued / chunks taken by load_chunk
-    int inflate_ahead = 2, inflate_streams = 2;    // inflates queued beyond the chunk being parsed; streams they alternate between (NGSQ_INFLATE_AHEAD, NGSQ_INFLATE_STREAMS: A/B measurements)
     DevBuf<uint8_t> d_rawb[NR];
-    hipStream_t inf_stream[2] = {nullptr, nullptr};
-    bool inf_low_priority = true;
+    hipStream_t inf_stream[2] = {nullptr, nullptr}; // the inflates alternate between them (low priority: start_ingest)
     hipEvent_t raw_free[NR] = {nullptr, nullptr, nullptr};
     bool raw_free_set[NR] = {false, false, false};
     uint8_t *raw = nullptr; // the inflated bytes being indexed / cut into batches: d_raw (sharded mode) or a view into a raw buffer
@@ -316,7 +313,7 @@ struct DeviceIngest {
         for (auto &q : inf_stream)
             if (q) {
                 (void)hipStreamSynchronize(q);
-                pool_stream_put(inf_low_priority, q);
+                pool_stream_put(true, q);
             }
         for (auto &e : h2d_done) pool_event_put(e);
         for (auto &e : inf_done) pool_event_put(e);
@@ -518,7 +515,7 @@ void reader_main(DeviceIngest *d, std::string path) {
     const size_t cap = 2 * d->comp_chunk;
     const uint64_t out_limit = d->raw_cap > 2 * CARRY_MAX ? d->raw_cap - CARRY_MAX : d->raw_cap / 2;
     constexpr size_t STEP = (size_t)32 << 20; // bytes framed and sent at a time
-    const uint64_t ramp_first = env_mb("NGSQ_RAMP_FIRST_MB", 32), ramp_shift = getenv("NGSQ_RAMP_SHIFT") ? (uint64_t)atoi(getenv("NGSQ_RAMP_SHIFT")) : 2; // (measurement aids)
+    constexpr uint64_t RAMP_FIRST = (uint64_t)32 << 20, RAMP_SHIFT = 2; // the first chunk's inflated bytes, log2 of the growth per chunk
     constexpr int NT_MAX = ReadPool::NT_MAX;
     // leave two cores of the quota to the thread that drives the GPU and to this one (it frames while the others read)
     // (the workers of a sharded run share the quota: ngsq_bam_shard_begin sets reader_threads)
@@ -532,22 +529,17 @@ void reader_main(DeviceIngest *d, std::string path) {
     const int fd = fileno(d->f);
     // this thread, its pread workers and the pinned buffers they fill: all on the device's NUMA node
     pin_to_device_node(d->ctx->device);
-    // ---- three ways for a chunk's bytes to reach the device (round 6; tools/reader_paths_probe.cpp):
-    //   mapped   the bytes are in the page cache: the chunk IS the file's mapping -- framed in place, copied to the device straight
-    //            from it (the runtime pins the pages it reads; no copy by the host: 30-38 GB per core-second against 12-14 through
-    //            pread, one thread instead of four)
-    //   direct   they are not: O_DIRECT reads into the pinned buffer -- no kernel copy, no page cache pollution (35 GB per
+    // ---- two ways for a chunk's bytes to reach the pinned buffer (round 6; tools/reader_paths_probe.cpp):
+    //   direct   they are not in the page cache: O_DIRECT reads -- no kernel copy, no page cache pollution (35 GB per
     //            core-second against 3.8 for buffered reads of a cold file, and the storage's full rate)
-    //   pread    buffered reads into the pinned buffer (rounds 1-5): mappings or O_DIRECT not available, NGSQ_READER_PATH=pread
-    const char *path_env = getenv("NGSQ_READER_PATH"); // measurement aid: mapped | direct | pread | auto
-    const std::string path_mode = path_env ? path_env : "auto";
+    //   pread    they are, or O_DIRECT is not available: buffered reads (rounds 1-5)
+    // The file's mapping serves only the residency probe below.
     const uint8_t *fmap = nullptr;
-    if (path_mode == "auto" || path_mode == "mapped") {
+    {
         void *m = d->file_size ? mmap(nullptr, d->file_size, PROT_READ, MAP_PRIVATE, fd, 0) : MAP_FAILED;
         if (m != MAP_FAILED) fmap = static_cast<const uint8_t *>(m);
     }
-    int fd_direct = -1;
-    if (path_mode == "auto" || path_mode == "direct") fd_direct = open(path.c_str(), O_RDONLY | O_DIRECT | O_CLOEXEC);
+    const int fd_direct = open(path.c_str(), O_RDONLY | O_DIRECT | O_CLOEXEC);
     struct Closer {
         const uint8_t *m;
         uint64_t n;
@@ -593,45 +585,39 @@ void reader_main(DeviceIngest *d, std::string path) {
         // (32 / 128 / 512 MiB): the first records reach the facets 15 ms into the scan.  (Twice its predecessor until the
         // decoder got faster in round 3 -- a chunk's fixed costs, launches and host round trips, then weighed more than the
         // shorter waits: 0.217-0.221 s -> 0.198-0.213 s for the 6 GB file.)
-        const uint64_t limit = chunk_no * ramp_shift < 12 ? std::min<uint64_t>(out_limit, (uint64_t)ramp_first << (chunk_no * ramp_shift)) : out_limit;
+        const uint64_t limit = chunk_no * RAMP_SHIFT < 12 ? std::min<uint64_t>(out_limit, RAMP_FIRST << (chunk_no * RAMP_SHIFT)) : out_limit;
         {
             std::unique_lock<std::mutex> g(d->mu);
             d->cv.wait(g, [&] { return d->stop || !c.ready; });
             if (d->stop) return;
         }
-        // ---- where this chunk's bytes are: in the page cache (then the chunk is the mapping), or not (pinned buffer, O_DIRECT)
+        // ---- where this chunk's bytes are: in the page cache (pread), or not (O_DIRECT)
         const uint64_t chunk_off = file_pos - leftover.size(); // file offset of the chunk's first byte
         {
             const uint64_t look = std::min<uint64_t>(d->pos_end, chunk_off + std::min<uint64_t>(cap, (uint64_t)256 << 20));
-            const double in_cache = (path_mode == "direct" || path_mode == "pread") ? 0.0 : resident(chunk_off, look);
-            // (auto does not take the mapped path: in the pipeline it is cheaper per byte than pread but slower on the wall -- 0.35-0.74 s
-            // against 0.20-0.33 s for the 6 GB file -- see the table in DESIGN.md section 8)
-            c.mapped = fmap && path_mode == "mapped";
-            cold = !c.mapped && fd_direct >= 0 && (path_mode == "direct" || in_cache < 0.5);
+            // (copying a warm chunk to the device straight from the mapping, framed in place, was measured in round 6: cheaper per
+            // byte than pread but slower on the wall -- 0.35-0.74 s against 0.20-0.33 s for the 6 GB file)
+            cold = fd_direct >= 0 && resident(chunk_off, look) < 0.5;
         }
-        if (!c.mapped) {
-            if (!c.pin && ngsq::pool_pinned_alloc((void **)&c.pin, cap + 8192, &c.h_bytes) != hipSuccess) {
-                {
-                    std::lock_guard<std::mutex> g(d->mu);
-                    c.err = path + ": hipHostMalloc of the ingest buffers failed";
-                    c.last = true;
-                    c.ready = true;
-                }
-                d->cv.notify_all();
-                return;
+        if (!c.pin && ngsq::pool_pinned_alloc((void **)&c.pin, cap + 8192, &c.h_bytes) != hipSuccess) {
+            {
+                std::lock_guard<std::mutex> g(d->mu);
+                c.err = path + ": hipHostMalloc of the ingest buffers failed";
+                c.last = true;
+                c.ready = true;
             }
-            if (!pool_open) {
-                pool.open(NT, fd);
-                pool_open = true;
-            }
-            c.h = c.pin + (chunk_off & 4095); // address == file offset (mod 4096): O_DIRECT reads whole sectors in place
-        } else {
-            c.h = const_cast<uint8_t *>(fmap) + chunk_off;
+            d->cv.notify_all();
+            return;
         }
+        if (!pool_open) {
+            pool.open(NT, fd);
+            pool_open = true;
+        }
+        c.h = c.pin + (chunk_off & 4095); // address == file offset (mod 4096): O_DIRECT reads whole sectors in place
         const double tr0 = now_ms();
         double t_frame = 0, t_send = 0, t_join = 0, t_spawn = 0;
         int n_steps = 0;
-        if (!c.mapped) memcpy(c.h, leftover.data(), leftover.size()); // (a mapped chunk simply starts that many bytes earlier in the file)
+        memcpy(c.h, leftover.data(), leftover.size());
         c.fill = leftover.size();
         c.file_off = file_pos - leftover.size();
         c.err.clear();
@@ -660,11 +646,7 @@ void reader_main(DeviceIngest *d, std::string path) {
         auto send = [&]() {
             if (h2d_ok && c.err.empty() && c.consumed > sent) {
                 const double ts = now_ms();
-                // (from the mapping: the runtime pins the pages it copies from and lets them go inside the call -- it returns when
-                // the bytes have left.  Registering the pieces ourselves and copying asynchronously crashed in the runtime when the
-                // consumer thread's calls ran beside it (round 6, not pursued: DESIGN.md section 8))
-                h2d_ok = (c.mapped ? hipMemcpyAsync(d->d_comp_slot[k].p + sent, c.h + sent, c.consumed - sent, hipMemcpyHostToDevice, d->copy_stream)
-                                   : ngsq::pool_pinned_h2d(d->d_comp_slot[k].p + sent, c.pin, (size_t)(c.h - c.pin) + sent, c.consumed - sent, d->copy_stream)) == hipSuccess;
+                h2d_ok = ngsq::pool_pinned_h2d(d->d_comp_slot[k].p + sent, c.pin, (size_t)(c.h - c.pin) + sent, c.consumed - sent, d->copy_stream) == hipSuccess;
                 sent = c.consumed;
                 t_send += now_ms() - ts;
             }
@@ -713,37 +695,23 @@ void reader_main(DeviceIngest *d, std::string path) {
             const size_t fill0 = c.fill;
             size_t avail = 0;
             bool short_read = false;
-            if (c.mapped) {
-                // nothing to read: the bytes are where they are; framed and sent STEP bytes at a time (the copies pin as they go)
-                const size_t have = (size_t)std::min<uint64_t>(want, d->file_size > file_pos ? d->file_size - file_pos : 0);
-                short_read = have < want;
-                while (avail < have) {
-                    avail = std::min(have, avail + STEP);
-                    c.fill = fill0 + avail;
-                    if (c.err.empty() && !full) {
-                        frame();
-                        send();
-                    }
+            pool.start(c.h + c.fill, file_pos, want, cold);
+            t_spawn += now_ms() - tsp;
+            // what has arrived is framed and sent while the rest is read, STEP bytes at a time
+            bool all = false;
+            while (!all) {
+                const double tj = now_ms();
+                pool.wait_prefix(std::min(want, avail + STEP), &avail, &all, &short_read);
+                t_join += now_ms() - tj;
+                c.fill = fill0 + avail;
+                if (c.err.empty() && !full) {
+                    frame();
+                    send();
                 }
-            } else {
-                pool.start(c.h + c.fill, file_pos, want, cold);
-                t_spawn += now_ms() - tsp;
-                // what has arrived is framed and sent while the rest is read, STEP bytes at a time
-                bool all = false;
-                while (!all) {
-                    const double tj = now_ms();
-                    pool.wait_prefix(std::min(want, avail + STEP), &avail, &all, &short_read);
-                    t_join += now_ms() - tj;
-                    c.fill = fill0 + avail;
-                    if (c.err.empty() && !full) {
-                        frame();
-                        send();
-                    }
-                }
-                if (pool.bad) c.err = "read error on " + path;
-                // (without O_DIRECT: below 1.2 GB/s per read thread the bytes did not come out of the page cache -- larger pieces then)
-                if (fd_direct < 0 && avail >= ((size_t)32 << 20)) cold = (double)avail / ((now_ms() - tsp) * 1e-3) < 1.2e9 * NT;
             }
+            if (pool.bad) c.err = "read error on " + path;
+            // (without O_DIRECT: below 1.2 GB/s per read thread the bytes did not come out of the page cache -- larger pieces then)
+            if (fd_direct < 0 && avail >= ((size_t)32 << 20)) cold = (double)avail / ((now_ms() - tsp) * 1e-3) < 1.2e9 * NT;
             if (avail < want || short_read) eof = true;
             file_pos += avail;
             if (file_pos >= d->pos_end) eof = true;
@@ -932,7 +900,7 @@ int issue_inflate(ngsq_bam *b, DeviceIngest *d, uint64_t j) {
     if (!p.err.empty() || !p.n_blk) return NGSQ_OK;
     p.blocks = c.blocks;
     p.coff = c.coff;
-    const int si = d->inflate_streams > 1 ? (int)(j & 1) : 0;
+    const int si = (int)(j & 1);
     hipStream_t sb = d->inf_stream[si];
     BHIP(d->d_status_s[k].reserve(p.n_blk + 1));
     if (p.status_cap < p.n_blk) {
@@ -962,8 +930,7 @@ int issue_inflate(ngsq_bam *b, DeviceIngest *d, uint64_t j) {
             BHIP(d->d_comp_slot[k].reserve(p.consumed + INFLATE_IN_SLACK));
             if (d->d_comp_slot[k].p != slot_was) BHIP(hipMemsetAsync(d->d_comp_slot[k].p, 0, d->d_comp_slot[k].bytes, sb));
         }
-        if (c.mapped) BHIP(hipMemcpyAsync(d->d_comp_slot[k].p, c.h, p.consumed, hipMemcpyHostToDevice, sb));
-        else BHIP(ngsq::pool_pinned_h2d(d->d_comp_slot[k].p, c.pin, (size_t)(c.h - c.pin), p.consumed, sb));
+        BHIP(ngsq::pool_pinned_h2d(d->d_comp_slot[k].p, c.pin, (size_t)(c.h - c.pin), p.consumed, sb));
         BHIP(launch_copy_words(d->d_blocks_s[k].p, dev_of(p.pin_blocks), p.n_blk * sizeof(BgzfBlock), sb));
         BHIP(launch_copy_words(d->d_coff_s[k].p, dev_of(p.pin_coff), p.n_blk * sizeof(uint64_t), sb));
     }
@@ -1035,7 +1002,7 @@ int load_chunk(ngsq_bam *b, DeviceIngest *d) {
     // stream) take the wave slots this chunk's leave when its last blocks are in work
     auto issue_ahead = [&]() -> int {
         if (p.last) return NGSQ_OK;
-        while (d->chunks_issued <= j + (uint64_t)d->inflate_ahead) {
+        while (d->chunks_issued <= j + DeviceIngest::INFLATE_AHEAD) {
             const uint64_t q = d->chunks_issued;
             const int kq = (int)(q % DeviceIngest::NC);
             if (q > j && d->pend[(q - 1) % DeviceIngest::NC].last) break; // (nothing behind the range's last chunk)
@@ -1257,19 +1224,15 @@ int start_ingest(ngsq_bam *b, ngsq_ctx *c, DeviceIngest *d) {
     {   // the inflate of the NEXT chunk runs beside the parse and the scan of this one, and it takes every
         // wave slot its LDS allows: give it the lowest priority so that the short kernels of the context's stream get
         // the slots its decoders free, instead of queueing behind all of them
-        const char *e = getenv("NGSQ_INFLATE_PRIORITY");
-        d->inf_low_priority = !(e && atoi(e) == 0); // =0: normal priority (A/B measurements)
         // (keeping the decoders off 8 / 16 / 32 compute units with a CU mask, so that the CRC and the parse kernels always find free
         // ones, was measured in round 5: 269 -> 210 / 210 / 204 M records/s on the plain file, 250 -> 194 / 198 / 200 M on the
         // aligner-style one -- masked streams cannot carry the low priority, and the decoders lose more than the others gain)
-        for (auto &q : d->inf_stream) BHIP(ngsq::pool_stream_get(d->inf_low_priority, &q));
+        for (auto &q : d->inf_stream) BHIP(ngsq::pool_stream_get(true, &q));
     }
     for (auto &e : d->h2d_done) BHIP(ngsq::pool_event_get(&e));
     for (auto &e : d->inf_done) BHIP(ngsq::pool_event_get(&e));
     for (auto &e : d->raw_free) BHIP(ngsq::pool_event_get(&e));
     for (auto &e : d->retired_ev) BHIP(ngsq::pool_event_get(&e));
-    if (const char *e = getenv("NGSQ_INFLATE_AHEAD")) d->inflate_ahead = std::max(1, std::min(2, atoi(e)));
-    if (const char *e = getenv("NGSQ_INFLATE_STREAMS")) d->inflate_streams = std::max(1, std::min(2, atoi(e)));
     // the reader starts pinning and reading at once; the two raw buffers are allocated meanwhile
     if (trace_on()) fprintf(stderr, "[ingest] +%.1f ms streams and events created\n", now_ms() - d->t_start);
     d->reader = std::thread(reader_main, d, b->path);

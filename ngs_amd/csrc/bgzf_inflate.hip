@@ -27,41 +27,12 @@
 //    (k_bgzf_crc: 64 slices per block, combined with GF(2) polynomial multiplication).
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-#include <cstdlib>
 #include <mutex>
 #include <vector>
 
 #include "ingest_kernels.h"
 
 namespace ngsq {
-
-// Build with -DNGSQ_INFLATE_PROFILE to accumulate s_memtime deltas per decoder phase (measurement aid
-// for DESIGN.md; the counters are read back by launch_bgzf_inflate and printed to stderr).
-#ifdef NGSQ_INFLATE_PROFILE
-__device__ unsigned long long g_inflate_prof[16];
-#define PROF_DECL unsigned long long prof_t = __builtin_readcyclecounter(), prof_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, prof_cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0}
-#define PROF(k)                                                     \
-    do {                                                            \
-        const unsigned long long now_ = __builtin_readcyclecounter(); \
-        prof_acc[k] += now_ - prof_t;                               \
-        prof_t = now_;                                              \
-    } while (0)
-#define PROF_COUNT(k, n) prof_cnt[k] += (n)
-#define PROF_FLUSH                                                                             \
-    do {                                                                                       \
-        if (lane == 0)                                                                         \
-            for (int k_ = 0; k_ < 8; k_++) {                                                   \
-                atomicAdd(&g_inflate_prof[k_], prof_acc[k_]);                                  \
-                atomicAdd(&g_inflate_prof[8 + k_], prof_cnt[k_]);                              \
-            }                                                                                  \
-    } while (0)
-#else
-#define PROF_DECL
-#define PROF(k)
-#define PROF_COUNT(k, n)
-#define PROF_FLUSH
-#endif
 
 namespace {
 
@@ -72,11 +43,8 @@ constexpr uint32_t LB = 10, DB = 8; // bits of the primary lookup tables
 // that is set by the LDS per decoder in 1280-byte granules: measured on the synthetic BAM (1.09 GB out,
 // 35 % of the matches reach beyond 2 KiB, 19 % beyond 4 KiB, 10 % beyond 8 KiB), same box, kernel time:
 // ring 8192 (12 decoders per CU) 24.6 ms, 4096 (17-19) 17.3 ms, 2048 (25) 14.7 ms, 1024 with a 7-bit distance
-// table (28, the register limit) 15.7 ms.  (-DNGSQ_INFLATE_RING=... to rebuild with another size, tools/ring_sweep.sh)
-#ifndef NGSQ_INFLATE_RING
-#define NGSQ_INFLATE_RING 2048
-#endif
-constexpr uint32_t RING = NGSQ_INFLATE_RING, RMASK = RING - 1;
+// table (28, the register limit) 15.7 ms.
+constexpr uint32_t RING = 2048, RMASK = RING - 1;
 constexpr uint32_t PIECE = RING / 4;  // bytes that leave the ring together
 
 // Table entries are 16 bits (LDS per decoder is what limits the decoders per CU).  The low seven bits of every entry are
@@ -580,12 +548,8 @@ __device__ __forceinline__ void inflate_block(Lds &L, const uint8_t *__restrict_
         // from this same wave: its stores and its L1-bypassing loads (sc1: served by this XCD's L2) take the same
         // path in order, so no fence is needed -- an agent-scope release here cost a write-back of the XCD's L2
         // (buffer_wbl2) and a drain of the wave's stores per KiB of output.
-#ifdef NGSQ_INFLATE_FENCE
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-#endif
     };
 
-    PROF_DECL;
     // ---- the decoded symbols and the emit
     // [0, pos) has been written (ring / HBM); the symbols in `qe` (lanes [0, nq), in stream order) cover [pos, dpos) without
     // gaps.  Entry: q_lit / q_match above.
@@ -627,14 +591,7 @@ __device__ __forceinline__ void inflate_block(Lds &L, const uint8_t *__restrict_
         const uint32_t T = base + lane, src = T - (oe >> 17) - 1u;
         const bool inchunk = active && !lit && (int32_t)(src - base) >= 0;
         uint32_t val = (oe >> 17) & 255u;
-#ifdef NGSQ_INFLATE_PROFILE
-        {   // (round 4: nine emits in ten of an aligner-style BAM hold bytes whose source has left the ring; 46 % of the output bytes)
-            const uint64_t farm = __ballot(active && !lit && !inchunk && (int32_t)(src - base + RING) < 0);
-            PROF_COUNT(3, farm != 0);
-            PROF_COUNT(4, __popcll(farm));
-            PROF_COUNT(5, __popcll(__ballot(inchunk)) != 0);
-        }
-#endif
+        // (round 4: nine emits in ten of an aligner-style BAM hold bytes whose source has left the ring; 46 % of the output bytes)
         if (active && !lit && !inchunk) {
             if (__builtin_expect((int32_t)(src - base + RING) < 0, 0))
                 val = __hip_atomic_load(gdst + src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -653,7 +610,6 @@ __device__ __forceinline__ void inflate_block(Lds &L, const uint8_t *__restrict_
         if (active) L.ring[T & RMASK] = (uint8_t)val;
         pos += n;
         while (pos - flushed >= PIECE) flush_piece(PIECE);
-        PROF_COUNT(2, 1);
     };
     // whole 64-byte chunks while there are any; all = everything decoded so far (before a stored block writes the ring, at
     // the end).  What is not written out completely moves to the first lanes: the symbols from the one that holds byte
@@ -673,7 +629,6 @@ __device__ __forceinline__ void inflate_block(Lds &L, const uint8_t *__restrict_
 
     bool last = false;
     while (!last && err == INF_OK) {
-        PROF(0); // other
         HeadBits hb(br);
         last = hb.take(1);
         const uint32_t type = hb.take(2);
@@ -798,7 +753,6 @@ __device__ __forceinline__ void inflate_block(Lds &L, const uint8_t *__restrict_
             err = INF_BAD_CODE_LENGTHS;
             break;
         }
-        PROF(1); // block header + tables
         // ---- the symbols of the block, in batches of up to 64
         // A window of 128 bits holds ~12 symbols, and decoding them where they were found -- at one lane in ten -- made the
         // decode, the prefix sum of the output lengths and the append a third of all instructions.  So it takes two phases:
@@ -812,7 +766,6 @@ __device__ __forceinline__ void inflate_block(Lds &L, const uint8_t *__restrict_
         //       the entries join the symbols left over from the last batch in `qe`.
         bool end_of_block = false;
         while (!end_of_block && err == INF_OK) {
-            PROF(5);
             br.sync();
             uint32_t np = nq, rel = 0; // symbols listed (the first nq are the ones in qe), window bits behind the bit position
             bool stopped = false;
@@ -831,8 +784,6 @@ __device__ __forceinline__ void inflate_block(Lds &L, const uint8_t *__restrict_
                     // bits to the next symbol, or a stop mark (bit 6: end of block, a distance with a long code, an invalid code)
                     step[h] = e_step(E) + (e_is_len(E) ? d_step(D) : 0u);
                 }
-                PROF(2); // window bits + gathers
-                PROF_COUNT(0, 1);
                 // the chain of real symbol starts: readlane + add per symbol, position after position
                 uint64_t syms[WH];
                 uint32_t s = 0; // bits of the window consumed
@@ -872,7 +823,6 @@ __device__ __forceinline__ void inflate_block(Lds &L, const uint8_t *__restrict_
                         }
                     }
                 }
-                PROF(3); // chain
                 {   // (the chain's lanes straight from the scalar mask, their rank among them by v_mbcnt: no vector compare)
                     uint32_t slot = np;
 #pragma unroll
@@ -884,7 +834,6 @@ __device__ __forceinline__ void inflate_block(Lds &L, const uint8_t *__restrict_
                 }
                 np += n_syms;
                 rel += s;
-                PROF(4); // list append
             }
             // phase 2
             if (np > nq) {
@@ -906,7 +855,6 @@ __device__ __forceinline__ void inflate_block(Lds &L, const uint8_t *__restrict_
                 const uint32_t incl = wave_inclusive_sum(olen);
                 const uint32_t at = dpos + incl - olen;
                 const uint32_t total = __builtin_amdgcn_readlane(incl, 63);
-                PROF_COUNT(1, __popcll(__ballot(fresh && is_lit)));
                 // a corrupt stream stops here, before anything of this batch is written: a distance beyond the
                 // start of the output would read in front of the block's buffer, and output beyond ISIZE would be flushed
                 // past its end
@@ -923,13 +871,11 @@ __device__ __forceinline__ void inflate_block(Lds &L, const uint8_t *__restrict_
                 dpos += total;
             }
             br.consume(rel);
-            PROF(6); // phase 2
             drain(false);
             if (stopped) {
                 // The chain stopped at a symbol the lanes could not finish: end of block, a long code (or a
                 // distance code with one), or an invalid code.  One symbol the plain way, into the next free lane of qe
                 // (fewer than 64 bytes are waiting there: fewer than 64 symbols).
-                PROF_COUNT(6, 1);
                 br.sync();
                 const uint32_t x0 = br.bits32();
                 const uint32_t e = uni(litlen_lookup(L, x0));
@@ -971,15 +917,12 @@ __device__ __forceinline__ void inflate_block(Lds &L, const uint8_t *__restrict_
         }
     }
     if (err == INF_OK) drain(true);
-    PROF(0);
     if (err == INF_OK && pos != isize) err = pos > isize ? INF_OUTPUT_OVERRUN : INF_SIZE_MISMATCH;
     if (err == INF_OK && br.consumed_bits() > bit_limit) err = INF_INPUT_OVERRUN;
     __syncthreads();
     if (err == INF_OK) {
         while (flushed < pos) flush_piece(min(pos - flushed, PIECE));
     }
-    PROF(7); // final flush + CRC
-    PROF_FLUSH;
     if (lane == 0) status[bi] = err;
 }
 
@@ -992,10 +935,8 @@ __device__ __forceinline__ void inflate_block(Lds &L, const uint8_t *__restrict_
 // wave slots and registers the decoders leave.  The counter also evens out the tail: no last partial round of blocks.
 // (registers: at most 80, for six decoders per SIMD -- left alone the compiler takes 92, mostly for scalars that no longer fit the
 // scalar file: five per SIMD, 20 per CU, 9 % slower)
-#ifndef NGSQ_INFLATE_WAVES
-#define NGSQ_INFLATE_WAVES 6
-#endif
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NGSQ_INFLATE_WAVES, 8))) void k_bgzf_inflate(const uint8_t *__restrict__ comp,
+constexpr uint32_t INFLATE_WAVES = 6;
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(INFLATE_WAVES, 8))) void k_bgzf_inflate(const uint8_t *__restrict__ comp,
                                                      const BgzfBlock *__restrict__ blocks, uint32_t n_blocks,
                                                      uint8_t *__restrict__ out, uint32_t *__restrict__ status,
                                                      uint32_t *__restrict__ next_block, uint32_t base) {
@@ -1021,7 +962,7 @@ constexpr uint32_t CRC_WAVES = 8; // BGZF blocks per workgroup: the tables are l
 constexpr uint32_t CRC_MAX_SLICE = 1024; // bytes of one of the 64 slices of a block (ISIZE <= 65536)
 __global__ __launch_bounds__(64 * CRC_WAVES) void k_bgzf_crc(const uint8_t *__restrict__ out, const BgzfBlock *__restrict__ blocks,
                                                              uint32_t n_blocks, uint32_t *__restrict__ status,
-                                                             const uint32_t *__restrict__ pow_tab, uint32_t *__restrict__ status_host, int skip) {
+                                                             const uint32_t *__restrict__ pow_tab, uint32_t *__restrict__ status_host) {
     NGSQ_FOREGROUND_WAVE();
     __shared__ uint32_t s_tab[CRC_SLICES * 256];
     for (uint32_t k = threadIdx.x; k < CRC_SLICES * 256; k += 64 * CRC_WAVES) s_tab[k] = c_crc.t[k >> 8][k & 0xFFu];
@@ -1036,10 +977,6 @@ __global__ __launch_bounds__(64 * CRC_WAVES) void k_bgzf_crc(const uint8_t *__re
             if (status_host && lane == 0) status_host[bi] = st0;
             return;
         }
-    }
-    if (skip) { // (NGSQ_CRC_SKIP=1, measurement aid: the verdicts travel, the checksum is not computed)
-        if (status_host && lane == 0) status_host[bi] = INF_OK;
-        return;
     }
     const uint8_t *p = out + uni64(blocks[bi].out_off);
     const uint32_t S = (isize + 63u) / 64u, pad = 64u * S - isize;
@@ -1112,8 +1049,7 @@ hipError_t launch_bgzf_crc(const BgzfBlock *blocks, uint32_t n_blocks, const uin
         }
         pow_tab = tab[dev];
     }
-    static const int skip = getenv("NGSQ_CRC_SKIP") && atoi(getenv("NGSQ_CRC_SKIP")) ? 1 : 0; // what the file path would gain if the CRC cost nothing
-    hipLaunchKernelGGL(k_bgzf_crc, dim3((n_blocks + CRC_WAVES - 1) / CRC_WAVES), dim3(64 * CRC_WAVES), 0, s, out, blocks, n_blocks, status, pow_tab, status_host, skip);
+    hipLaunchKernelGGL(k_bgzf_crc, dim3((n_blocks + CRC_WAVES - 1) / CRC_WAVES), dim3(64 * CRC_WAVES), 0, s, out, blocks, n_blocks, status, pow_tab, status_host);
     return hipGetLastError();
 }
 
@@ -1127,10 +1063,9 @@ hipError_t launch_bgzf_inflate(const uint8_t *comp, const BgzfBlock *blocks, uin
         (void)hipGetDevice(&dev);
         (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
         // decoders per CU: what the LDS holds (160 KiB / 6400-byte allocations = 25), less one so that every SIMD keeps
-        // registers and a wave slot for the other stream's kernels (NGSQ_INFLATE_PER_CU: measurement aid)
-        uint32_t per_cu = 24;
-        if (const char *v = getenv("NGSQ_INFLATE_PER_CU")) per_cu = (uint32_t)atoi(v); // 0: a workgroup per block, as before
-        resident = per_cu ? (uint32_t)n_cu * per_cu : 0xFFFFFFFFu;
+        // registers and a wave slot for the other stream's kernels
+        constexpr uint32_t per_cu = 24;
+        resident = (uint32_t)n_cu * per_cu;
         attr = true;
     }
     const uint32_t grid = n_blocks < resident ? n_blocks : resident;
@@ -1149,23 +1084,6 @@ hipError_t launch_bgzf_inflate(const uint8_t *comp, const BgzfBlock *blocks, uin
         if (counter_base) *counter_base = base + n_blocks + grid;
     }
     if (check_crc) (void)launch_bgzf_crc(blocks, n_blocks, out, status, nullptr, s);
-#ifdef NGSQ_INFLATE_PROFILE
-    {
-        unsigned long long h[16];
-        (void)hipStreamSynchronize(s);
-        (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_inflate_prof), sizeof h);
-        static const char *names[8] = {"other", "header+tables", "window: table reads", "window: chain", "window: list append", "emit",
-                                       "batch decode", "final flush"};
-        unsigned long long tot = 0;
-        for (int k = 0; k < 8; k++) tot += h[k];
-        for (int k = 0; k < 8; k++)
-            fprintf(stderr, "[inflate-prof] %-24s %6.2f %%\n", names[k], tot ? 100.0 * (double)h[k] / (double)tot : 0.0);
-        fprintf(stderr, "[inflate-prof] windows %llu, literals %llu, emits %llu, symbols taken the plain way %llu\n", h[8], h[9], h[10], h[14]);
-        fprintf(stderr, "[inflate-prof] emits with bytes read back from HBM %llu (%llu bytes), emits with a source inside their own 64 bytes %llu\n", h[11], h[12], h[13]);
-        unsigned long long z[16] = {0};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_inflate_prof), z, sizeof z);
-    }
-#endif
     return hipGetLastError();
 }
 

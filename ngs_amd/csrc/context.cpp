@@ -125,13 +125,6 @@ uint32_t ngsq_gc_offset(uint64_t seed, uint64_t idx, uint32_t l) { return ngsq_g
 
 static uint64_t round_up(uint64_t v, uint64_t m) { return (v + m - 1) / m * m; }
 
-// NGSQ_STEP_LEGACY=1 (measurement aid): ngsq_reset and ngsq_finalize as they were until round 4 -- one hipMemsetAsync per small
-// block, one device-to-host copy per result block -- for an A/B of the time a step spends outside its kernels
-static bool step_legacy() {
-    static const bool v = [] { const char *e = getenv("NGSQ_STEP_LEGACY"); return e && atoi(e) != 0; }();
-    return v;
-}
-
 int ngsq_create(const ngsq_config *cfg, ngsq_ctx **out) {
     if (!cfg || !out) return fail(nullptr, NGSQ_ERR_INVALID_ARGUMENT, "null argument");
     *out = nullptr;
@@ -1013,41 +1006,29 @@ int ngsq_finalize(ngsq_ctx *c) {
     const bool cov = (facets & NGSQ_FACET_COVERAGE) && c->n_chunks;
     const uint64_t n_bins = cov ? c->bin_off[nr] + 1 : 0, n_hist = cov ? c->n_cov_hist : 0, n_vaf = (facets & NGSQ_FACET_EDITS) ? NGSQ_VAF_BINS : 0;
     const uint64_t need = c->n_counters + n_hist + n_bins + n_vaf + 2;
-    if (step_legacy()) {
-        if (cov) {
-            HIP_TRY(c, hipMemcpyAsync(c->h_cov_hist.data(), c->d_cov_hist, c->n_cov_hist * 8, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(c, hipMemcpyAsync(c->h_bin_totals.data(), c->d_bin_totals, c->bin_off[nr] * 8 + 8, hipMemcpyDeviceToHost, c->stream));
-        }
-        if (n_vaf) HIP_TRY(c, hipMemcpyAsync(c->h_vaf.data(), c->d_vaf, NGSQ_VAF_BINS * 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(c->h_touched, c->d_touched, 16, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(c->h_counters.data(), c->st.counters, c->n_counters * 8, hipMemcpyDeviceToHost, c->stream));
-    } else {
-        if (c->pin_words < need) {
-            if (c->pin_results) (void)hipHostFree(c->pin_results);
-            c->pin_results = nullptr;
-            c->pin_words = 0;
-            HIP_TRY(c, hipHostMalloc((void **)&c->pin_results, (need + need / 4) * 8, hipHostMallocMapped));
-            HIP_TRY(c, hipHostGetDevicePointer((void **)&c->pin_results_dev, c->pin_results, 0));
-            c->pin_words = need + need / 4;
-        }
-        unsigned long long *d = c->pin_results_dev;
-        StateSpans sp;
-        sp.copy(d, c->st.counters, c->n_counters * 2);
-        sp.copy(d + c->n_counters, c->d_cov_hist, n_hist * 2);
-        sp.copy(d + c->n_counters + n_hist, c->d_bin_totals, n_bins * 2);
-        sp.copy(d + c->n_counters + n_hist + n_bins, c->d_vaf, n_vaf * 2);
-        sp.copy(d + c->n_counters + n_hist + n_bins + n_vaf, c->d_touched, 4);
-        HIP_TRY(c, launch_state_spans(sp, c->stream));
+    if (c->pin_words < need) {
+        if (c->pin_results) (void)hipHostFree(c->pin_results);
+        c->pin_results = nullptr;
+        c->pin_words = 0;
+        HIP_TRY(c, hipHostMalloc((void **)&c->pin_results, (need + need / 4) * 8, hipHostMallocMapped));
+        HIP_TRY(c, hipHostGetDevicePointer((void **)&c->pin_results_dev, c->pin_results, 0));
+        c->pin_words = need + need / 4;
     }
+    unsigned long long *d = c->pin_results_dev;
+    StateSpans sp;
+    sp.copy(d, c->st.counters, c->n_counters * 2);
+    sp.copy(d + c->n_counters, c->d_cov_hist, n_hist * 2);
+    sp.copy(d + c->n_counters + n_hist, c->d_bin_totals, n_bins * 2);
+    sp.copy(d + c->n_counters + n_hist + n_bins, c->d_vaf, n_vaf * 2);
+    sp.copy(d + c->n_counters + n_hist + n_bins + n_vaf, c->d_touched, 4);
+    HIP_TRY(c, launch_state_spans(sp, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (!step_legacy()) {
-        const unsigned long long *h = c->pin_results;
-        memcpy(c->h_counters.data(), h, c->n_counters * 8);
-        if (n_hist) memcpy(c->h_cov_hist.data(), h + c->n_counters, n_hist * 8);
-        if (n_bins) memcpy(c->h_bin_totals.data(), h + c->n_counters + n_hist, n_bins * 8);
-        if (n_vaf) memcpy(c->h_vaf.data(), h + c->n_counters + n_hist + n_bins, n_vaf * 8);
-        memcpy(c->h_touched, h + c->n_counters + n_hist + n_bins + n_vaf, 16);
-    }
+    const unsigned long long *h = c->pin_results;
+    memcpy(c->h_counters.data(), h, c->n_counters * 8);
+    if (n_hist) memcpy(c->h_cov_hist.data(), h + c->n_counters, n_hist * 8);
+    if (n_bins) memcpy(c->h_bin_totals.data(), h + c->n_counters + n_hist, n_bins * 8);
+    if (n_vaf) memcpy(c->h_vaf.data(), h + c->n_counters + n_hist + n_bins, n_vaf * 8);
+    memcpy(c->h_touched, h + c->n_counters + n_hist + n_bins + n_vaf, 16);
     resolve_timing(c);
     c->finalized = true;
     if ((facets & NGSQ_FACET_COVERAGE) && c->n_chunks) { // algorithmic bytes of the scan: 8 B per torn-down position
@@ -1135,33 +1116,21 @@ int ngsq_reset(ngsq_ctx *c) {
     if (!c) return NGSQ_ERR_INVALID_ARGUMENT;
     HIP_TRY(c, hipSetDevice(c->device));
     const uint64_t nr4 = round_up(c->st.n_refs ? c->st.n_refs : 1, 4);
-    if (step_legacy()) {
-        HIP_TRY(c, hipMemsetAsync(c->st.counters, 0, c->n_counters * 8, c->stream));
-        if (c->n_depth && c->finalized) HIP_TRY(c, hipMemsetAsync(c->st.chunk_sums, 0, (c->n_depth - c->n_diff) * 4, c->stream));
-        HIP_TRY(c, hipMemsetAsync(c->d_td, 0, c->n_td * 8, c->stream));
-        if (c->stream_cov) {
-            HIP_TRY(c, hipMemsetAsync(c->d_stream_u32, 0, (7 * nr4 + 4) * 4, c->stream));
-            HIP_TRY(c, hipMemsetAsync(c->csa.plan_a, 0xFF, nr4 * 4, c->stream));
-            HIP_TRY(c, hipMemsetAsync(c->d_last_key, 0, 8, c->stream));
-            HIP_TRY(c, hipMemsetAsync(c->d_chunk_flags, 0, c->n_chunks ? c->n_chunks : 1, c->stream));
-        }
-    } else {
-        // every small block in one launch (kernels.hip k_state_spans); the two large ones below stay memsets
-        StateSpans sp;
-        sp.fill(c->st.counters, c->n_counters * 2, 0);
-        if (c->n_depth && c->finalized) sp.fill(c->st.chunk_sums, c->n_depth - c->n_diff, 0);
-        sp.fill(c->d_td, c->n_td * 2, 0);
-        if (c->stream_cov) {
-            sp.fill(c->d_stream_u32, 2 * nr4, 0);            // end_acc | prev_end
-            sp.fill(c->csa.plan_a, nr4, 0xFFFFFFFFu);        // CS_NONE
-            sp.fill(c->csa.plan_z, 4 * nr4 + 4, 0);          // plan_z | plan_h | plan_t | guard_until | the two largest-span words
-            sp.fill(c->d_last_key, 2, 0);
-            sp.fill(c->d_chunk_flags, (c->n_chunks + 3) / 4, 0);
-        }
-        sp.fill(c->d_touched, 2, 0xFFFFFFFFu);               // {~0, 0}
-        sp.fill(c->d_touched + 1, 2, 0);
-        HIP_TRY(c, launch_state_spans(sp, c->stream));
+    // every small block in one launch (kernels.hip k_state_spans); the two large ones below stay memsets
+    StateSpans sp;
+    sp.fill(c->st.counters, c->n_counters * 2, 0);
+    if (c->n_depth && c->finalized) sp.fill(c->st.chunk_sums, c->n_depth - c->n_diff, 0);
+    sp.fill(c->d_td, c->n_td * 2, 0);
+    if (c->stream_cov) {
+        sp.fill(c->d_stream_u32, 2 * nr4, 0);            // end_acc | prev_end
+        sp.fill(c->csa.plan_a, nr4, 0xFFFFFFFFu);        // CS_NONE
+        sp.fill(c->csa.plan_z, 4 * nr4 + 4, 0);          // plan_z | plan_h | plan_t | guard_until | the two largest-span words
+        sp.fill(c->d_last_key, 2, 0);
+        sp.fill(c->d_chunk_flags, (c->n_chunks + 3) / 4, 0);
     }
+    sp.fill(c->d_touched, 2, 0xFFFFFFFFu);               // {~0, 0}
+    sp.fill(c->d_touched + 1, 2, 0);
+    HIP_TRY(c, launch_state_spans(sp, c->stream));
     if (c->n_depth) {
         if (!c->finalized) {
             HIP_TRY(c, hipMemsetAsync(c->st.depth, 0, c->n_depth * 4, c->stream));
@@ -1183,7 +1152,6 @@ int ngsq_reset(ngsq_ctx *c) {
     }
     c->h_touched[0] = ~0ull;
     c->h_touched[1] = 0;
-    if (step_legacy()) HIP_TRY(c, hipMemcpyAsync(c->d_touched, c->h_touched, 16, hipMemcpyHostToDevice, c->stream));
     for (const ngsq_ctx::DeferredFeatures &d : c->ft_deferred) ngsq::pool_device_free(d.buf, d.bytes); // (frees behind a device sync)
     c->ft_deferred.clear();
     c->span_turn = 0;

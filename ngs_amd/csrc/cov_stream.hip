@@ -39,30 +39,15 @@ typedef unsigned long long u64;
 
 constexpr uint32_t ST_THREADS = 256;
 constexpr uint32_t ST_WAVES = ST_THREADS / 64;
-#ifndef ST_W_N
-#define ST_W_N 1024
-#endif
-constexpr uint32_t ST_W = ST_W_N; // positions of one wave's LDS window
-#ifndef ST_LIST_N
-#define ST_LIST_N 232
-#endif
-#ifndef ST_HOT_BINS_N
-#define ST_HOT_BINS_N 64
-#endif
-constexpr uint32_t ST_LIST = ST_LIST_N;  // entries of a wave's list of open ends (a deeper pile walks back instead)
+constexpr uint32_t ST_W = 1024; // positions of one wave's LDS window
+constexpr uint32_t ST_LIST = 232; // entries of a wave's list of open ends (a deeper pile walks back instead)
 // The depths of neighbouring positions are a dozen values around the running depth: 64 lanes adding to the
 // histogram word of their depth serialise on those few words (74 % of this kernel's LDS time were same-address
 // conflicts).  So the tally goes to a HOT window first: ST_HOT_BINS bins around the running depth, ST_HOT_REP
 // copies of each (lane & 3 picks the copy), re-anchored when the depth at the start of a pass drifts out of its
 // middle three quarters -- the copies are then summed into the wave's histogram.  Depths outside the window go to the
 // histogram directly, in the same instruction (one address select per lane, no branch).
-#ifndef ST_HOT_REP_N
-#define ST_HOT_REP_N 4
-#endif
-constexpr uint32_t ST_HOT_BINS = ST_HOT_BINS_N, ST_HOT_REP = ST_HOT_REP_N, ST_HOT = ST_HOT_BINS * ST_HOT_REP;
-#ifndef ST_EXP
-#define ST_EXP 0 // measurement builds only (tools/exp_stream.sh): 1 no look-back, 2 no prefix passes, 3 no histogram atomics, 4 neither
-#endif
+constexpr uint32_t ST_HOT_BINS = 64, ST_HOT_REP = 4, ST_HOT = ST_HOT_BINS * ST_HOT_REP;
 
 __device__ __forceinline__ u64 st_key(int32_t rf, int32_t ps) { // as in k_fields<STREAM>
     return rf < 0 ? 0xFFFFFFFF00000000ull : ((u64)(uint32_t)rf << 32) | (uint32_t)(ps + 1);
@@ -178,9 +163,7 @@ struct StTileIn {
     int32_t rf_t, ps_t, rf_n, ps_n;  // first record of the tile and of its successor
 };
 
-#ifndef ST_MIN_BLOCKS
-#define ST_MIN_BLOCKS 4
-#endif
+constexpr uint32_t ST_MIN_BLOCKS = 4;
 __global__ __launch_bounds__(ST_THREADS, ST_MIN_BLOCKS) void k_cov_stream(DeviceState st, DeviceBatch b, CovStreamArgs a) {
     NGSQ_FOREGROUND_WAVE();
     extern __shared__ __attribute__((aligned(16))) uint32_t s_dyn[];
@@ -404,7 +387,7 @@ __global__ __launch_bounds__(ST_THREADS, ST_MIN_BLOCKS) void k_cov_stream(Device
                 if (rec[j] && sp >= w && sp < wend) atomicAdd(&win[sp - w], 1u);
                 if (rec[j] && e[j] >= w && e[j] < wend) atomicAdd(&win[e[j] - w], 0xFFFFFFFFu);
             }
-            if (lb_reach >= w && ST_EXP != 1 && ST_EXP != 4) { // earlier tiles' records that reach into [lo, hi); >=: an end exactly on w still owes its -1
+            if (lb_reach >= w) { // earlier tiles' records that reach into [lo, hi); >=: an end exactly on w still owes its -1
                 uint32_t reach = 0;
                 if (from_list) {
                     if (first && lane == 0 && lst_n) atomicAdd(&win[0], lst_n); // they all start before lo
@@ -514,7 +497,7 @@ __global__ __launch_bounds__(ST_THREADS, ST_MIN_BLOCKS) void k_cov_stream(Device
                     const uint32_t one = i < len && depth != 0 ? 1u : 0u;
                     const bool in_hot = depth - hot_base < ST_HOT_BINS;
                     const uint32_t word = !one ? lane : in_hot ? hot_lane + depth * ST_HOT_REP : bin < hw ? bin : bin - hw;
-                    if (ST_EXP != 3) atomicAdd(&hist[word], in_hot || bin < hw ? one : one << 16);
+                    atomicAdd(&hist[word], in_hot || bin < hw ? one : one << 16);
                     lsum += i < len ? depth : 0u;
                 }
                 if (in_acc) {
@@ -528,7 +511,7 @@ __global__ __launch_bounds__(ST_THREADS, ST_MIN_BLOCKS) void k_cov_stream(Device
                 }
                 since_flush += 64 * PL;
             };
-            for (uint32_t pb = 0; pb < len && ST_EXP != 2 && ST_EXP != 4;) {
+            for (uint32_t pb = 0; pb < len;) {
                 const uint32_t rem = len - pb;
                 if (rem > 256) {
                     pass(std::integral_constant<uint32_t, 8>{}, pb);
@@ -567,7 +550,6 @@ __global__ __launch_bounds__(ST_THREADS, ST_MIN_BLOCKS) void k_cov_stream(Device
         }
 
         // ---- the list for the next tile: what was open in front and still is beyond hi, plus this tile's records
-        if (ST_EXP == 1 || ST_EXP == 4) return;
         if (from_list) {
             for (uint32_t c = 0; c < lst_n; c += 64) {
                 const uint32_t ee = c + lane < lst_n ? lst[c + lane] : 0u;

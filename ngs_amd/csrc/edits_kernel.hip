@@ -32,10 +32,6 @@ typedef unsigned long long u64;
 
 namespace {
 
-#ifndef EDITS_EXP
-#define EDITS_EXP 0 // measurement builds only: 1 = no atomics for the mismatches, 2 = no cover (window, flush), 3 = no comparison, 4 = neither 1 nor 2;
-                    // k_edits_rows: 5 = the cover window is not flushed to global memory, 6 = the alts window is not, 7 = neither
-#endif
 constexpr uint32_t ED_THREADS = 256;
 constexpr uint32_t ED_PASSES = 4;                      // records per thread and tile: lane + 64 * pass of the wave's 256 consecutive records
 constexpr uint32_t ED_WAVE_TILE = 64 * ED_PASSES;
@@ -159,14 +155,14 @@ __device__ __forceinline__ uint32_t ed_walk_record(const DeviceState &st, const 
                     if (m - ju < 8u) xx[u] &= 0xFFFFFFFFu << (4u * (8u - (m - ju)));
                     uint32_t t = nz_nibbles(xx[u]);
                     edits += (uint32_t)__popc(t);
-                    while (t && EDITS_EXP != 1 && EDITS_EXP != 4) {
+                    while (t) {
                         const uint32_t q = 7u - ((uint32_t)__builtin_ctz(t) >> 2); // the first base of the window is the top nibble
                         t &= t - 1;
                         atomicAdd(&alts[p0 + 1 + ju + q], 1u);
                     }
                 }
             }
-            if (m && EDITS_EXP != 2 && EDITS_EXP != 4) {
+            if (m) {
                 atomicAdd(&diff[p0], 1u);
                 atomicAdd(&diff[p0 + m], 0xFFFFFFFFu);
                 st.counters[st.off_eseen + ref] = 1ull; // (a plain store: the sequence has Edits state)
@@ -292,7 +288,7 @@ __global__ __launch_bounds__(ED_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
             // bases substituted: 38.8 ms per 100 M; emptying the list as it fills, inside the comparison: 32 ms, and 4 % slower on
             // the reads the kernel is built for -- measured in round 5, not kept)
             auto drain = [&]() {
-                for (uint32_t k = 0; k < cnt && EDITS_EXP != 1 && EDITS_EXP != 4; k++) {
+                for (uint32_t k = 0; k < cnt; k++) {
                     const uint2 en = list[64 * k];
                     uint32_t t = nz_nibbles(en.x);
                     uint32_t *const alts = st.edits + meta_eoff + ((uint64_t)meta_L + 1) + (uint64_t)(en.y >> 16 ? P2 : P1) + 1 + 8 * (en.y & 0xFFFFu);
@@ -308,7 +304,7 @@ __global__ __launch_bounds__(ED_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
             for (uint32_t seg = 0; seg < (m2 ? 2u : 1u); seg++) {
                 const uint32_t v0 = seg ? m + ins : a, v1 = seg ? r.l : a + m, P = seg ? P2 : P1;
                 const uint8_t *const rb = (P & 1u ? st.ref_bases_odd : st.ref_bases) + meta_boff + (P >> 1);
-                for (uint32_t c0 = v0 >> 5; c0 * 32 < v1 && EDITS_EXP != 3; c0 += ED_CHUNKS) {
+                for (uint32_t c0 = v0 >> 5; c0 * 32 < v1; c0 += ED_CHUNKS) {
                     uint4 sv[ED_CHUNKS], rv[ED_CHUNKS];
 #pragma unroll
                     for (uint32_t k = 0; k < ED_CHUNKS; k++) {
@@ -342,22 +338,20 @@ __global__ __launch_bounds__(ED_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
             }
             if (cnt > ED_LIST) return true; // more mismatching dwords than the list holds: the walk does this record
             drain();
-            if (EDITS_EXP != 2 && EDITS_EXP != 4) {
-                atomicAdd(&win[i0], 1u);
-                atomicAdd(&win[i1], 0xFFFFFFFFu);
-                top = max(top, (uint32_t)i1);
-                if (m2) { // the second M's cover: in the window when it reaches that far, else straight to the array (a skip of kilobases)
-                    const uint64_t q0 = i1 + gap, q1 = q0 + m2;
-                    if (q1 < ED_WINDOW) {
-                        atomicAdd(&win[q0], 1u);
-                        atomicAdd(&win[q1], 0xFFFFFFFFu);
-                        top = max(top, (uint32_t)q1);
-                    } else {
-                        uint32_t *const diff = st.edits + meta_eoff + win_base;
-                        atomicAdd(&diff[q0], 1u);
-                        atomicAdd(&diff[q1], 0xFFFFFFFFu);
-                        st.counters[st.off_eseen + win_ref] = 1ull;
-                    }
+            atomicAdd(&win[i0], 1u);
+            atomicAdd(&win[i1], 0xFFFFFFFFu);
+            top = max(top, (uint32_t)i1);
+            if (m2) { // the second M's cover: in the window when it reaches that far, else straight to the array (a skip of kilobases)
+                const uint64_t q0 = i1 + gap, q1 = q0 + m2;
+                if (q1 < ED_WINDOW) {
+                    atomicAdd(&win[q0], 1u);
+                    atomicAdd(&win[q1], 0xFFFFFFFFu);
+                    top = max(top, (uint32_t)q1);
+                } else {
+                    uint32_t *const diff = st.edits + meta_eoff + win_base;
+                    atomicAdd(&diff[q0], 1u);
+                    atomicAdd(&diff[q1], 0xFFFFFFFFu);
+                    st.counters[st.off_eseen + win_ref] = 1ull;
                 }
             }
             if (edits > 512u) c[3] += 1;
@@ -462,20 +456,12 @@ __global__ __launch_bounds__(ED_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
 // ---------------------------------------------------------------------------
 constexpr uint32_t ED_NW = 5;                    // windows per row the kernel is built for (reads of up to 160 bases)
 constexpr uint32_t EDR_TILE = ED_THREADS * 4;    // records a block is launched for (the grid; the waves cut their runs of passes themselves)
-#ifndef NGSQ_EDR_WINDOW
-#define NGSQ_EDR_WINDOW 1408 // (1536 until the histograms and the GC tally took 2.8 KB more: the block's LDS stays at 32 granules of 1280 bytes, four blocks per CU)
-#endif
 // waves per SIMD the register allocation is made for: four, what the block's LDS allows (the variant that also tallies GC Content
 // takes 143-148 registers when left alone -- three waves per SIMD: 3.9 ms per 100 M reads against 3.56 at four; the plain variant
-// fits by itself).  NGSQ_EDR_WAVES: measurement builds.
-#ifndef NGSQ_EDR_FAR
-#define NGSQ_EDR_FAR 1 // measurement builds: 0 = a read whose first M reaches beyond the wave's window is the walk kernel's
-#endif
-#ifndef NGSQ_EDR_WAVES
-#define NGSQ_EDR_WAVES 4
-#endif
-#define EDR_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(NGSQ_EDR_WAVES, NGSQ_EDR_WAVES)))
-constexpr uint32_t EDR_WINDOW = NGSQ_EDR_WINDOW;            // entries of the wave's cover window (256 sorted reads: 790 positions at 60x, 1430 at 30x: there the last few reads of a tile go to the walk)
+// fits by itself)
+constexpr uint32_t EDR_WAVES = 4;
+// (1536 until the histograms and the GC tally took 2.8 KB more: the block's LDS stays at 32 granules of 1280 bytes, four blocks per CU)
+constexpr uint32_t EDR_WINDOW = 1408;            // entries of the wave's cover window (256 sorted reads: 790 positions at 60x, 1430 at 30x: there the last few reads of a tile go to the walk)
 constexpr uint32_t GC_NONE = 0x3FFu;             // "no GC window": an offset whose window lies behind every 16-byte window of a row
 constexpr uint32_t GC_HW = (NGSQ_GC_BINS + 1) / 2; // words of a 101-bin histogram of 16-bit pairs
 
@@ -506,7 +492,7 @@ constexpr uint32_t EDG_WINDOW = 1152; // RAGGED: entries of the wave's cover win
 // Until then this layout went through k_edits, a lane per RECORD: 64 lanes 25..150 bytes apart per load instruction, 11.1 ms per
 // 100 M reads of 50-300 bases, and 32 ms with 5 % of their bases substituted (no alts window in LDS there).
 template <bool CIG_OFF, bool GC, bool RAGGED>
-__global__ __launch_bounds__(ED_THREADS) EDR_WAVES_ATTR void k_edits_rows(DeviceState st, DeviceBatch b, uint32_t R, uint32_t recip, u64 *__restrict__ defer_bits) {
+__global__ __launch_bounds__(ED_THREADS) __attribute__((amdgpu_waves_per_eu(EDR_WAVES, EDR_WAVES))) void k_edits_rows(DeviceState st, DeviceBatch b, uint32_t R, uint32_t recip, u64 *__restrict__ defer_bits) {
     NGSQ_FOREGROUND_WAVE();
     __shared__ uint32_t s_h1[ED_HW], s_h2[ED_HW];               // per-read edit counts, 16-bit pairs
     static_assert(!(GC && RAGGED), "the GC tally is fused into the fixed-pitch variants only");
@@ -653,14 +639,14 @@ __global__ __launch_bounds__(ED_THREADS) EDR_WAVES_ATTR void k_edits_rows(Device
                 for (uint32_t k = 0; k < 4; k++) {
                     const uint32_t i = ib + 64 * k + lane;
                     if (v[k]) {
-                        if (EDITS_EXP != 5 && EDITS_EXP != 7) atomicAdd(&dst[i], v[k]);
+                        atomicAdd(&dst[i], v[k]);
                         win[i] = 0;
                     }
                 }
             }
             // The alts window: two 16-bit counters per LDS word = two neighbouring 32-bit entries of the global array, added with ONE
             // 64-bit atomic (counts stay far below 2^32, so nothing carries from the low entry into the high one).  The flush is paid
-            // per atomic instruction and line, not per lane (EDITS_EXP 6: the alts' flush cost as much as the cover's although only one
+            // per atomic instruction and line, not per lane (measured: the alts' flush cost as much as the cover's although only one
             // position in four holds a mismatch), so this halves it.  Whether a window word's two entries share an aligned 8 bytes
             // depends on the sequence's place in the block: if not, a lane adds the high half of the word before its own and the
             // low half of its own.  (A mismatch lies below the end of its read's M: below `top`.)
@@ -679,7 +665,7 @@ __global__ __launch_bounds__(ED_THREADS) EDR_WAVES_ATTR void k_edits_rows(Device
                     v = (u64)(before >> 16) | (u64)(own & 0xFFFFu) << 32;
                     at = adst + 2 * i - 1;
                 }
-                if (v && EDITS_EXP != 6 && EDITS_EXP != 7) atomicAdd(reinterpret_cast<u64 *>(at), v);
+                if (v) atomicAdd(reinterpret_cast<u64 *>(at), v);
             }
             for (uint32_t ib = 0; ib < n_dw; ib += 64) // (behind the adds: a lane reads its neighbour's word above)
                 if (ib + lane < n_dw && ib + lane < ALTW) altw[ib + lane] = 0;
@@ -847,30 +833,28 @@ __global__ __launch_bounds__(ED_THREADS) EDR_WAVES_ATTR void k_edits_rows(Device
                 // walk + 7.3 ms here per 100 M reads spread over the 3.1 Gbp of a real header (bench.py whole_genome).
                 const bool far1 = i0 + m >= WIN; // (then far2 as well: i1 >= i0 + m)
                 own = shape && m && (uint64_t)a + m + z == r.l && holds && r.ref == win_ref && (uint32_t)r.pos >= a + win_base && e <= meta_E &&
-                      (!far1 || (NGSQ_EDR_FAR && i0 < (1u << 14) - 1024u));
+                      (!far1 || i0 < (1u << 14) - 1024u);
                 if (own) {
                     // the record's descriptor for the window lanes: where its base 0 lies in the packed reference (a byte offset
                     // from ref_bases: the copy that starts at base P & 1), compared bases [v0, v1), window entry of base 0
                     P = (uint32_t)r.pos - a;
                     vv = a | (a + m) << 9 | (P - win_base) << 18;
                     P = (uint32_t)(meta_boff + (P >> 1)) + (P & 1u ? odd_delta : 0u);
-                    if (EDITS_EXP != 2 && EDITS_EXP != 4) {
-                        if (!far1) {
-                            atomicAdd(&win[i0], 1u);
-                            atomicAdd(&win[i0 + m], 0xFFFFFFFFu);
-                        } else {
-                            uint32_t *const diff = st.edits + meta_eoff + win_base;
-                            atomicAdd(&diff[i0], 1u);
-                            atomicAdd(&diff[i0 + m], 0xFFFFFFFFu);
-                        }
-                        if (m2 && !far2) {
-                            atomicAdd(&win[i0 + m + del], 1u);
-                            atomicAdd(&win[i1], 0xFFFFFFFFu);
-                        } else if (m2) {
-                            uint32_t *const diff = st.edits + meta_eoff + win_base;
-                            atomicAdd(&diff[i0 + m + del], 1u);
-                            atomicAdd(&diff[i1], 0xFFFFFFFFu);
-                        }
+                    if (!far1) {
+                        atomicAdd(&win[i0], 1u);
+                        atomicAdd(&win[i0 + m], 0xFFFFFFFFu);
+                    } else {
+                        uint32_t *const diff = st.edits + meta_eoff + win_base;
+                        atomicAdd(&diff[i0], 1u);
+                        atomicAdd(&diff[i0 + m], 0xFFFFFFFFu);
+                    }
+                    if (m2 && !far2) {
+                        atomicAdd(&win[i0 + m + del], 1u);
+                        atomicAdd(&win[i1], 0xFFFFFFFFu);
+                    } else if (m2) {
+                        uint32_t *const diff = st.edits + meta_eoff + win_base;
+                        atomicAdd(&diff[i0 + m + del], 1u);
+                        atomicAdd(&diff[i1], 0xFFFFFFFFu);
                     }
                     top = max(top, (uint32_t)(far2 || far1 ? WIN - 1 : i1)); // (far: the mismatches below the window's end are tallied in it)
                     // what step 2c needs of the record: first M's length, insertion, parity of P; the gap in an array of its own
@@ -924,7 +908,7 @@ __global__ __launch_bounds__(ED_THREADS) EDR_WAVES_ATTR void k_edits_rows(Device
                 if (n_steps > 1) wb = begin_win();
             }
             // ---- 2b. lane = window: 16 bytes of sequence XOR 16 of the reference
-            auto compare_win = [&](const Win &w, const bool far = false) { // far (2c only): the window may lie beyond the wave's LDS window
+            auto compare_win = [&](const Win &w) { // (a far first M's window, or 2c's, may lie beyond the wave's LDS window)
                 if (GC) { // the window's share of its record's GC window
                     const uint32_t glo = (w.lohi >> 16) & 0xFFu, ghi = w.lohi >> 24;
                     if (ghi > glo) {
@@ -950,11 +934,11 @@ __global__ __launch_bounds__(ED_THREADS) EDR_WAVES_ATTR void k_edits_rows(Device
                 uint32_t t = ((n0 >> 3) | (n1 >> 2) | (n2 >> 1) | n3) & s_tmask[(w.lohi >> 8) & 0xFFu] & ~s_tmask[w.lohi & 0xFFu];
                 if (t) {
                     atomicAdd(&red[w.slot], (uint32_t)__popc(t));
-                    while (t && EDITS_EXP != 1 && EDITS_EXP != 4) {
+                    while (t) {
                         const uint32_t bit = (uint32_t)__builtin_ctz(t);
                         t &= t - 1;
                         const uint32_t x0e = w.x0 + 8 * (bit & 3u) + ((bit >> 2) ^ 1u); // window entry of the 0-based position
-                        if (far && x0e >= WIN) atomicAdd(st.edits + meta_eoff + win_base + ((uint64_t)meta_L + 1) + 1 + x0e, 1u); // alts[1 + position]
+                        if (x0e >= WIN) atomicAdd(st.edits + meta_eoff + win_base + ((uint64_t)meta_L + 1) + 1 + x0e, 1u); // alts[1 + position]
                         else atomicAdd(&altw[x0e >> 1], 1u << (16u * (x0e & 1u)));
                     }
                 }
@@ -965,19 +949,19 @@ __global__ __launch_bounds__(ED_THREADS) EDR_WAVES_ATTR void k_edits_rows(Device
             if (n_steps > 1) finish_win(wb);
             if (it + 1 < ppw) cur = load_cols(r0 + 64); // in flight while this pass is compared (behind the end: the last record again)
 #pragma unroll 1
-            for (uint32_t k = 0; k < n_steps && EDITS_EXP != 3; k += 3) {
+            for (uint32_t k = 0; k < n_steps; k += 3) {
                 if (k + 2 < n_steps) wc = load_win();
-                compare_win(wa, NGSQ_EDR_FAR != 0);
+                compare_win(wa);
                 if (k + 1 >= n_steps) break;
                 if (k + 3 < n_steps) wa = load_win();
-                compare_win(wb, NGSQ_EDR_FAR != 0);
+                compare_win(wb);
                 if (k + 2 >= n_steps) break;
                 if (k + 4 < n_steps) wb = load_win();
-                compare_win(wc, NGSQ_EDR_FAR != 0);
+                compare_win(wc);
             }
             // ---- 2c. the second M of the records that have one: lane = window ww of the e-th such record (its row once more, the
             // reference del - ins bases further on -- the other packed copy when that is odd)
-            if (imask && EDITS_EXP != 3) {
+            if (imask) {
                 const uint32_t n_ind = (uint32_t)__popcll(imask);
                 for (uint32_t g = lane; g < n_ind * (RAGGED ? EDG_MAXW : R); g += 64) {
                     const uint32_t ei = RAGGED ? g / EDG_MAXW : (g * recip) >> 16, ww = RAGGED ? g % EDG_MAXW : g - ei * R, rr = ilist[ei];
@@ -996,7 +980,7 @@ __global__ __launch_bounds__(ED_THREADS) EDR_WAVES_ATTR void k_edits_rows(Device
                     w.x0 = (uint32_t)((int32_t)(d.y >> 18) + shift + (int32_t)b0);
                     const uint32_t lo = min(v0 > b0 ? v0 - b0 : 0u, 32u), hi = min(v1 > b0 ? v1 - b0 : 0u, 32u);
                     w.lohi = lo | hi << 8;
-                    compare_win(w, true);
+                    compare_win(w);
                 }
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -1306,19 +1290,14 @@ static bool edits_rows_ok(const DeviceState &st, const DeviceBatch &b) {
 static bool edits_ragged_ok(const DeviceState &st, const DeviceBatch &b) { return b.seq_off && edits_windows_ok(st, b); }
 
 bool edits_can_take_gc(const DeviceState &st, const DeviceBatch &b) {
-    static const bool off = getenv("NGSQ_EDITS_NO_GC") && atoi(getenv("NGSQ_EDITS_NO_GC")); // A/B measurements: k_gc as a kernel of its own
-    return !off && b.n && st.ref_bases && edits_rows_ok(st, b);
+    return b.n && st.ref_bases && edits_rows_ok(st, b);
 }
 
 hipError_t launch_edits(const LaunchInfo &li, const DeviceState &st, const DeviceBatch &b, unsigned long long *defer_bits, bool with_gc, hipStream_t s) {
     if (!b.n) return hipSuccess;
-    static int per_cu = -1;
-    if (per_cu < 0) {
-        const char *e = getenv("NGSQ_EDITS_BLOCKS_PER_CU"); // measurement aid
-        per_cu = e && atoi(e) > 0 ? atoi(e) : 8;
-    }
+    constexpr uint64_t per_cu = 8;
     uint64_t g = (b.n + ED_TILE - 1) / ED_TILE;
-    const uint64_t cap = (uint64_t)li.n_cu * (uint32_t)per_cu;
+    const uint64_t cap = (uint64_t)li.n_cu * per_cu;
     if (g > cap) g = cap;
     const uint32_t R = (b.seq_stride + 15) / 16;
     const uint32_t gr = (uint32_t)std::min<uint64_t>((b.n + EDR_TILE - 1) / EDR_TILE, cap);

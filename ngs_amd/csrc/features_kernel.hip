@@ -18,8 +18,6 @@
 // correct: their brackets are the whole lists.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include <algorithm>
 
 #include "kernels.h"
@@ -115,10 +113,7 @@ __device__ __forceinline__ uint32_t wave_extreme(uint32_t v) {
 // by cross-lane reductions, the searches by its lanes 0..19, which keep their own previous result in a register as the next
 // tile's hint, the brackets handed to the records' searches as SCALARS (v_readlane: the names are uniform) -- so no wave ever
 // waits for another one's L2 probes, and the kernel has no LDS traffic and no barrier inside its loop.
-#ifndef NGSQ_FEATURES_RPT
-#define NGSQ_FEATURES_RPT 4
-#endif
-constexpr uint32_t F_RPT = NGSQ_FEATURES_RPT;
+constexpr uint32_t F_RPT = 4;
 __global__ __launch_bounds__(256) void k_features(DeviceState st, DeviceBatch b, FeatureTables ft) {
     NGSQ_FOREGROUND_WAVE();
     __shared__ uint32_t s_cnt[11];
@@ -382,14 +377,10 @@ hipError_t launch_features(const LaunchInfo &li, const DeviceState &st, const De
     // 7 (what is resident at once) -> 2.33, 8 -> 2.13 (a second round with one block per CU), 9 -> 2.02, 10 -> 1.91,
     // 11 -> 1.78, 12 -> 1.73, 14 -> 1.85, 20 -> 1.78, 24 -> 1.76; the same order on 10 M.  Seven resident blocks are slower
     // than six (28 waves per CU wait on each other's L2 probes); a grid of nearly two rounds evens out the slices that meet
-    // long gene lists.  NGSQ_FEATURES_BLOCKS_PER_CU: measurement aid.
-    static int per_cu = 0;
-    if (!per_cu) {
-        const char *e = getenv("NGSQ_FEATURES_BLOCKS_PER_CU");
-        per_cu = e && atoi(e) > 0 ? atoi(e) : 12;
-    }
+    // long gene lists.
+    constexpr uint64_t per_cu = 12;
     uint64_t g = (b.n + 256 * F_RPT - 1) / (256 * F_RPT); // four waves per block, a tile of 64 x F_RPT records each
-    if (g > (uint64_t)li.n_cu * (uint64_t)per_cu) g = (uint64_t)li.n_cu * (uint64_t)per_cu;
+    if (g > (uint64_t)li.n_cu * per_cu) g = (uint64_t)li.n_cu * per_cu;
     hipLaunchKernelGGL(k_features, dim3((uint32_t)g), dim3(256), 0, s, st, b, ft);
     return hipGetLastError();
 }

@@ -32,9 +32,6 @@ namespace ngsq {
 
 typedef unsigned long long u64;
 
-#ifndef NGSQ_FT_PREFETCH_OFFS
-#define NGSQ_FT_PREFETCH_OFFS 1 // 0: the offsets are loaded when the tile is processed (A/B builds)
-#endif
 constexpr uint32_t FT_THREADS = 256;
 constexpr uint32_t FT_PER_THREAD = 4;
 constexpr uint32_t FT_TILE = FT_THREADS * FT_PER_THREAD; // records per tile
@@ -158,7 +155,7 @@ __global__ __launch_bounds__(FT_THREADS, 4) void k_fields(DeviceState st, Device
         if (a.do_cov) r.pos = *reinterpret_cast<const int4 *>(b.pos + r0);
         r.co0 = 0;
         r.co_base = 0;
-        if (CIG_OFF && NGSQ_FT_PREFETCH_OFFS && (a.do_general || a.do_cov)) {
+        if (CIG_OFF && (a.do_general || a.do_cov)) {
             // Round 5: the thread's FIRST offset comes with the tile (a tile ahead), as a 32-bit distance from the tile's first (a scalar
             // load); the other three follow from the n_cigar column, which is here anyway -- so the operations are requested at the
             // top of process() instead of behind a load of their own.  (All five offsets prefetched cost ten registers held across
@@ -321,7 +318,7 @@ __global__ __launch_bounds__(FT_THREADS, 4) void k_fields(DeviceState st, Device
         uint32_t cigf[FT_PER_THREAD] = {0, 0, 0, 0}, cig2[FT_PER_THREAD] = {0, 0, 0, 0}, cig3[FT_PER_THREAD] = {0, 0, 0, 0};
         if (CIG_OFF && (a.do_general || a.do_cov)) {
             const bool saturated = ncig[0] == 0xFFFFu || ncig[1] == 0xFFFFu || ncig[2] == 0xFFFFu || ncig[3] == 0xFFFFu; // (the count is in the offsets then)
-            if (full_tile && NGSQ_FT_PREFETCH_OFFS && !saturated) {
+            if (full_tile && !saturated) {
                 coff[0] = raw.co_base + raw.co0;
 #pragma unroll
                 for (uint32_t j = 0; j < FT_PER_THREAD; j++) coff[j + 1] = coff[j] + ncig[j];

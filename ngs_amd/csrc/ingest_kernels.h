@@ -5,18 +5,11 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
-// The kernels of the context's stream (record index, columns, facets) share the CUs with the BGZF decoders of the next chunk
-// (another stream, persistent waves that keep the scalar and vector issue ports busy): their waves ask for the highest
-// issue priority, or a latency-bound kernel like the record-chain walk runs ten times slower beside the decoders than alone.
-#ifndef NGSQ_FOREGROUND_WAVE
-#define NGSQ_FOREGROUND_WAVE() __builtin_amdgcn_s_setprio(3)
-#endif
+#include "kernels.h" // NGSQ_FOREGROUND_WAVE
 
 // Every vector-memory operation this wave has issued (loads, stores, atomics without a result) has been acknowledged by the L2
 // when this returns: orders device-scope atomics in front of a later one without a release fence (k_rec_fixed's ticket).
-#ifndef NGSQ_WAIT_VMEM
 #define NGSQ_WAIT_VMEM() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#endif
 
 namespace ngsq {
 
@@ -62,10 +55,7 @@ hipError_t launch_bgzf_inflate(const uint8_t *comp, const BgzfBlock *blocks, uin
 hipError_t launch_bgzf_crc(const BgzfBlock *blocks, uint32_t n_blocks, const uint8_t *out, uint32_t *status, uint32_t *status_host, hipStream_t s);
 
 // ---- BAM record parse (csrc/bam_device.hip) -------------------------------------------------------
-#ifndef NGSQ_REC_SEGMENT
-#define NGSQ_REC_SEGMENT 16384
-#endif
-constexpr uint64_t REC_SEGMENT = NGSQ_REC_SEGMENT; // bytes of the inflated stream whose record chain is found as one (by its own lanes of a wave)
+constexpr uint64_t REC_SEGMENT = 16384; // bytes of the inflated stream whose record chain is found as one (by its own lanes of a wave)
 constexpr uint32_t REC_GROUP = 4;        // segments per wave of k_rec_candidates
 constexpr uint32_t REC_CANDIDATES = 2;   // chain starts kept per segment
 constexpr uint32_t REC_PIECES = (uint32_t)(REC_SEGMENT / 4096); // a segment's chain is written out by that many lanes, 4 KiB each

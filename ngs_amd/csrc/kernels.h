@@ -29,9 +29,7 @@
 // The kernels of the context's stream (record index, columns, facets) share the CUs with the BGZF decoders of the next chunk
 // (another stream, persistent waves that keep the scalar and vector issue ports busy): their waves ask for the highest
 // issue priority, or a latency-bound kernel like the record-chain walk runs ten times slower beside the decoders than alone.
-#ifndef NGSQ_FOREGROUND_WAVE
 #define NGSQ_FOREGROUND_WAVE() __builtin_amdgcn_s_setprio(3)
-#endif
 
 namespace ngsq {
 
@@ -176,8 +174,7 @@ hipError_t launch_qual(const LaunchInfo &li, const DeviceState &st, const Device
                        hipStream_t s);
 // Quality Score fast path for fixed-pitch rows (qual_kernel.hip)
 bool qual_window_supported(const DeviceState &st, const DeviceBatch &b);
-hipError_t launch_qual_window(const LaunchInfo &li, const DeviceState &st, const DeviceBatch &b, uint32_t nrot,
-                              hipStream_t s);
+hipError_t launch_qual_window(const LaunchInfo &li, const DeviceState &st, const DeviceBatch &b, hipStream_t s);
 // Genomic Features (features.rs:115-242): gene model as sorted coordinate lists, features_kernel.hip
 struct FeatureTables {
     // intervals of name id k on sequence r: entries [idx[k * n_refs + r], idx[k * n_refs + r + 1]) of

@@ -6,8 +6,6 @@
 // device-scope atomics.  No MFMA anywhere.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "../../include/ngsq_shared.h"
 #include "kernels.h"
 
@@ -75,9 +73,6 @@ __device__ __forceinline__ void gc_dword(uint32_t x, uint32_t mask, uint32_t &gc
     at += __popc((x ^ u) & ~(y | z) & mask); // nibble == 0001 or 1000
 }
 
-#ifndef NGSQ_GC_AHEAD
-#define NGSQ_GC_AHEAD 1 // measurement builds: 0 = every load when its turn comes
-#endif
 // Round 6: what says WHERE a record's window lies -- its flag, its length, its row's offset, its identity -- is requested an
 // iteration ahead, unconditionally and from a clamped index (a load under a branch gets a wait of its own from this compiler,
 // DESIGN 5.8; for the same reason OFFS / RID -- the batch has seq_off / record_id -- are compile-time).  An iteration used to
@@ -113,15 +108,10 @@ __global__ __launch_bounds__(256) void k_gc(DeviceState st, DeviceBatch b, uint6
     };
     const uint64_t step = blockDim.x, i0 = lo + threadIdx.x;
     Info nx{0, 0, 0, 0};
-    if (NGSQ_GC_AHEAD && i0 < hi) nx = fetch(i0);
+    if (i0 < hi) nx = fetch(i0);
     for (uint64_t i = i0; i < hi; i += step) {
-        Info r;
-        if (NGSQ_GC_AHEAD) {
-            r = nx;
-            nx = fetch(i + step < hi ? i + step : i); // (behind the slice: this record's columns again)
-        } else {
-            r = fetch(i);
-        }
+        const Info r = nx;
+        nx = fetch(i + step < hi ? i + step : i); // (behind the slice: this record's columns again)
         if (r.f & 0x500u) { // duplicate | secondary  gc_content.rs:41-45
             c[4] += 1;
             continue;
@@ -257,14 +247,7 @@ hipError_t launch_gc(const LaunchInfo &li, const DeviceState &st, const DeviceBa
 hipError_t launch_qual(const LaunchInfo &li, const DeviceState &st, const DeviceBatch &b, hipStream_t s) {
     if (!b.n) return hipSuccess;
     // fast path: fixed-pitch rows no longer than the table (qual_kernel.hip)
-    if (qual_window_supported(st, b)) {
-        static int nrot = -1;
-        if (nrot < 0) {
-            const char *e = getenv("NGSQ_QUAL_NROT"); // measurement knob; default 4
-            nrot = e ? atoi(e) : 4;
-        }
-        return launch_qual_window(li, st, b, (uint32_t)nrot, s);
-    }
+    if (qual_window_supported(st, b)) return launch_qual_window(li, st, b, s);
     if (qual_ragged_supported(st, b)) return launch_qual_ragged(li, st, b, s);
     uint32_t rows = b.qual_off ? st.max_read_len : b.qual_stride;
     if (rows > st.max_read_len) rows = st.max_read_len;

@@ -8,8 +8,7 @@
 //  k_qual_perm  rows of up to 256 bytes.  thread = one 16-byte WINDOW (record, w) of
 //               a row, w fixed per thread; ONE v_perm_b32 per byte builds the LDS
 //               address of its (cycle, score) cell; see the comment above the kernel.
-//  k_qual_win   rows of 257..320 bytes (and the measurement knob NGSQ_QUAL_NROT):
-//               the same window-per-thread shape with a [q][kb * RP + w] table
+//  k_qual_win   rows of 257..320 bytes: the same window-per-thread shape with a [q][kb * RP + w] table
 //               and two VALU operations per byte.
 //
 // Shared design points:
@@ -35,7 +34,7 @@ namespace ngsq {
 typedef unsigned long long u64;
 
 // row pitch (in words) between consecutive kb rows of one score: >= R, chosen so
-// that the NROT rotated records of a 32-lane group land on disjoint bank ranges
+// that the four rotated records of a 32-lane group land on disjoint bank ranges
 __host__ __device__ constexpr uint32_t qw_rp(uint32_t R) {
     // 4*RP mod 32 is the bank distance between two consecutive rotation positions; take the
     // smallest RP >= R whose circular distance from 0 is at least min(R, 12) banks
@@ -50,7 +49,7 @@ __host__ __device__ constexpr uint32_t qw_cp(uint32_t R) { return (16 * qw_rp(R)
 
 uint32_t qual_window_lds_bytes(uint32_t R) { return QUAL_BINS * qw_cp(R) * 4; }
 
-template <uint32_t R, uint32_t NROT>
+template <uint32_t R>
 __global__ __launch_bounds__(1024) void k_qual_win(DeviceState st, const uint8_t *__restrict__ qual, uint64_t n_rec,
                                                    uint32_t pitch) {
     NGSQ_FOREGROUND_WAVE();
@@ -101,28 +100,20 @@ __global__ __launch_bounds__(1024) void k_qual_win(DeviceState st, const uint8_t
             // table but are never read back.
             const uint32_t wbase = 4u * w_;
             uint32_t x[4], bd[4];
-            if (NROT == 1) {
-#pragma unroll
-                for (uint32_t d = 0; d < 4; d++) {
-                    x[d] = ww[d];
-                    bd[d] = wbase + d * S4;
-                }
-            } else {
-                // step d takes dword d ^ rot of the window (a bijection in d and in rot): lanes of the
-                // up to four records of a 32-lane group never update the same table word in one instruction
-                const bool r1 = rot_ & 1u, r2 = (NROT == 4) && (rot_ & 2u);
-                const uint32_t y0 = r2 ? ww[2] : ww[0], y1 = r2 ? ww[3] : ww[1], y2 = r2 ? ww[0] : ww[2],
-                               y3 = r2 ? ww[1] : ww[3];
-                x[0] = r1 ? y1 : y0;
-                x[1] = r1 ? y0 : y1;
-                x[2] = r1 ? y3 : y2;
-                x[3] = r1 ? y2 : y3;
-                const uint32_t h = r2 ? 2u * S4 : 0u, l = r1 ? S4 : 0u;
-                bd[0] = wbase + h + l;
-                bd[1] = wbase + h + (S4 - l);
-                bd[2] = wbase + (2u * S4 - h) + l;
-                bd[3] = wbase + (2u * S4 - h) + (S4 - l);
-            }
+            // step d takes dword d ^ rot of the window (a bijection in d and in rot): lanes of the
+            // up to four records of a 32-lane group never update the same table word in one instruction
+            const bool r1 = rot_ & 1u, r2 = rot_ & 2u;
+            const uint32_t y0 = r2 ? ww[2] : ww[0], y1 = r2 ? ww[3] : ww[1], y2 = r2 ? ww[0] : ww[2],
+                           y3 = r2 ? ww[1] : ww[3];
+            x[0] = r1 ? y1 : y0;
+            x[1] = r1 ? y0 : y1;
+            x[2] = r1 ? y3 : y2;
+            x[3] = r1 ? y2 : y3;
+            const uint32_t h = r2 ? 2u * S4 : 0u, l = r1 ? S4 : 0u;
+            bd[0] = wbase + h + l;
+            bd[1] = wbase + h + (S4 - l);
+            bd[2] = wbase + (2u * S4 - h) + l;
+            bd[3] = wbase + (2u * S4 - h) + (S4 - l);
 #pragma unroll
             for (uint32_t d = 0; d < 4; d++) {
 #pragma unroll
@@ -220,7 +211,7 @@ __device__ __forceinline__ uint32_t qr_from_lane(uint32_t v, uint32_t src_lane) 
     return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(src_lane << 2), (int)v);
 }
 
-template <uint32_t R, uint32_t NROT>
+template <uint32_t R>
 __global__ __launch_bounds__(1024) void k_qual_ragged(DeviceState st, const uint8_t *__restrict__ qual,
                                                       const uint64_t *__restrict__ qual_off, uint64_t n_rec) {
     NGSQ_FOREGROUND_WAVE();
@@ -362,26 +353,18 @@ __global__ __launch_bounds__(1024) void k_qual_ragged(DeviceState st, const uint
                 uint32_t x[4], bd[4];
 #pragma unroll
                 for (uint32_t d = 0; d < 4; d++) ww[d] = (ww[d] & keep[d]) | (~keep[d] & (QR_TRASH * 0x01010101u)); // (v_bfi_b32)
-                if (NROT == 1) {
-#pragma unroll
-                    for (uint32_t d = 0; d < 4; d++) {
-                        x[d] = ww[d];
-                        bd[d] = wbase + d * S4;
-                    }
-                } else {
-                    const bool r1 = rot & 1u, r2 = (NROT == 4) && (rot & 2u);
-                    const uint32_t y0 = r2 ? ww[2] : ww[0], y1 = r2 ? ww[3] : ww[1], y2 = r2 ? ww[0] : ww[2],
-                                   y3 = r2 ? ww[1] : ww[3];
-                    x[0] = r1 ? y1 : y0;
-                    x[1] = r1 ? y0 : y1;
-                    x[2] = r1 ? y3 : y2;
-                    x[3] = r1 ? y2 : y3;
-                    const uint32_t h = r2 ? 2u * S4 : 0u, l = r1 ? S4 : 0u;
-                    bd[0] = wbase + h + l;
-                    bd[1] = wbase + h + (S4 - l);
-                    bd[2] = wbase + (2u * S4 - h) + l;
-                    bd[3] = wbase + (2u * S4 - h) + (S4 - l);
-                }
+                const bool r1 = rot & 1u, r2 = rot & 2u;
+                const uint32_t y0 = r2 ? ww[2] : ww[0], y1 = r2 ? ww[3] : ww[1], y2 = r2 ? ww[0] : ww[2],
+                               y3 = r2 ? ww[1] : ww[3];
+                x[0] = r1 ? y1 : y0;
+                x[1] = r1 ? y0 : y1;
+                x[2] = r1 ? y3 : y2;
+                x[3] = r1 ? y2 : y3;
+                const uint32_t h = r2 ? 2u * S4 : 0u, l = r1 ? S4 : 0u;
+                bd[0] = wbase + h + l;
+                bd[1] = wbase + h + (S4 - l);
+                bd[2] = wbase + (2u * S4 - h) + l;
+                bd[3] = wbase + (2u * S4 - h) + (S4 - l);
 #pragma unroll
                 for (uint32_t d = 0; d < 4; d++) {
 #pragma unroll
@@ -417,15 +400,12 @@ __global__ __launch_bounds__(1024) void k_qual_ragged(DeviceState st, const uint
     if (lane == 0 && r1) atomicAdd(&st.counters[C_ERR + E_READ_TOO_LONG], (u64)r1);
 }
 
-#ifndef NGSQ_QR_NROT
-#define NGSQ_QR_NROT 4 // dword orders the records of a wave rotate through (1, 2 or 4: measurement builds)
-#endif
 template <uint32_t R>
 static hipError_t launch_ragged_r(const LaunchInfo &li, const DeviceState &st, const DeviceBatch &b, hipStream_t s) {
     const uint32_t lds = qr_table_bytes(R) + 16u * 64u * R + 17u * 16u; // table + one window->record byte map per wave + the keep masks
     static bool attr = false;
     if (!attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_qual_ragged<R, NGSQ_QR_NROT>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_qual_ragged<R>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
         attr = true;
@@ -434,7 +414,7 @@ static hipError_t launch_ragged_r(const LaunchInfo &li, const DeviceState &st, c
     uint64_t g = (b.n + 1023) / 1024;
     if (g > (uint64_t)li.n_cu * per_cu) g = (uint64_t)li.n_cu * per_cu;
     if (g < 1) g = 1;
-    hipLaunchKernelGGL((k_qual_ragged<R, NGSQ_QR_NROT>), dim3((uint32_t)g), dim3(1024), lds, s, st, b.qual, b.qual_off, b.n);
+    hipLaunchKernelGGL((k_qual_ragged<R>), dim3((uint32_t)g), dim3(1024), lds, s, st, b.qual, b.qual_off, b.n);
     return hipGetLastError();
 }
 
@@ -634,12 +614,12 @@ static hipError_t dispatch_perm(uint32_t R, const LaunchInfo &li, const DeviceSt
     }
 }
 
-template <uint32_t R, uint32_t NROT>
+template <uint32_t R>
 static hipError_t launch_r(const LaunchInfo &li, const DeviceState &st, const DeviceBatch &b, hipStream_t s) {
     const uint32_t lds = qual_window_lds_bytes(R);
     static bool attr = false;
     if (!attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_qual_win<R, NROT>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_qual_win<R>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
         attr = true;
@@ -648,16 +628,15 @@ static hipError_t launch_r(const LaunchInfo &li, const DeviceState &st, const De
     uint64_t g = (b.n * R + 1023) / 1024;
     if (g > (uint64_t)li.n_cu * per_cu) g = (uint64_t)li.n_cu * per_cu;
     if (g < 1) g = 1;
-    hipLaunchKernelGGL((k_qual_win<R, NROT>), dim3((uint32_t)g), dim3(1024), lds, s, st, b.qual, b.n, b.qual_stride);
+    hipLaunchKernelGGL((k_qual_win<R>), dim3((uint32_t)g), dim3(1024), lds, s, st, b.qual, b.n, b.qual_stride);
     return hipGetLastError();
 }
 
-template <uint32_t NROT>
 static hipError_t dispatch(uint32_t R, const LaunchInfo &li, const DeviceState &st, const DeviceBatch &b,
                            hipStream_t s) {
     switch (R) {
 #define CASE(r) \
-    case r: return launch_r<r, NROT>(li, st, b, s);
+    case r: return launch_r<r>(li, st, b, s);
         CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) CASE(13)
         CASE(14) CASE(15) CASE(16) CASE(17) CASE(18) CASE(19) CASE(20)
 #undef CASE
@@ -669,17 +648,12 @@ bool qual_window_supported(const DeviceState &st, const DeviceBatch &b) {
     return !b.qual_off && b.qual_stride >= 1 && b.qual_stride <= st.max_read_len && b.qual_stride <= 16 * QUAL_WIN_MAX_R;
 }
 
-hipError_t launch_qual_window(const LaunchInfo &li, const DeviceState &st, const DeviceBatch &b, uint32_t nrot,
-                              hipStream_t s) {
+hipError_t launch_qual_window(const LaunchInfo &li, const DeviceState &st, const DeviceBatch &b, hipStream_t s) {
     const uint32_t R = (b.qual_stride + 15) / 16;
     // two windows in flight per thread: depths 1..3, one or two blocks per CU, nontemporal loads and a
     // block-interleaved row order all measured within 2 % of each other
     if (R <= QP_MAX_R) return dispatch_perm<2>(R, li, st, b, s);
-    switch (nrot) {
-    case 1: return dispatch<1>(R, li, st, b, s);
-    case 2: return dispatch<2>(R, li, st, b, s);
-    default: return dispatch<4>(R, li, st, b, s);
-    }
+    return dispatch(R, li, st, b, s);
 }
 
 } // namespace ngsq
