@@ -1,0 +1,360 @@
+// bai.cpp -- ngsq_bam_build_index (include/ngsq_index.h): the device ingest hands out the file's records batch by batch,
+// bai_kernel.hip turns every batch into runs of (sequence, bin) and linear-index windows on the device, and the host
+// writes the BAI from the run list and the windows -- it never walks the records.  DESIGN.md section 12.
+#include <hip/hip_runtime_api.h>
+#include <stdlib.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/ngsq_index.h"
+#include "bai_kernels.h"
+#include "bam_reader.h"
+#include "bgzf.h"
+#include "context.h"
+#include "mem_pool.h"
+
+using namespace ngsq;
+
+namespace {
+
+double now_ms() {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// a device array from the process's block cache; grow() keeps the contents
+template <typename T> struct DevArr {
+    T *p = nullptr;
+    size_t cap = 0, bytes = 0;
+    hipError_t reserve(size_t n, hipStream_t s = nullptr, bool keep = false) {
+        if (n <= cap) return hipSuccess;
+        const size_t want = std::max(n + 64, cap * 2);
+        void *q = nullptr;
+        size_t got = 0;
+        hipError_t e = pool_device_alloc(&q, want * sizeof(T), &got);
+        if (e != hipSuccess) return e;
+        if (keep && p && cap) {
+            e = hipMemcpyAsync(q, p, cap * sizeof(T), hipMemcpyDeviceToDevice, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s); // (the old block goes back to the cache below)
+            if (e != hipSuccess) {
+                pool_device_free(q, got);
+                return e;
+            }
+        }
+        pool_device_free(p, bytes);
+        p = static_cast<T *>(q);
+        cap = got / sizeof(T);
+        bytes = got;
+        return hipSuccess;
+    }
+    ~DevArr() { pool_device_free(p, bytes); }
+};
+
+struct Pinned {
+    unsigned long long *h = nullptr, *dev = nullptr;
+    ~Pinned() {
+        if (h) (void)hipHostFree(h);
+    }
+};
+
+#define IHIP(expr)                                                                                           \
+    do {                                                                                                     \
+        hipError_t e_ = (expr);                                                                              \
+        if (e_ != hipSuccess) return ngsq_bam_fail(NGSQ_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+// @HD ... SO:coordinate (the reference: header.header().sort_order() == Coordinate)
+bool header_coordinate_sorted(const std::string &text) {
+    const size_t hd = text.rfind("@HD", 0) == 0 ? 0 : text.find("\n@HD");
+    if (hd == std::string::npos) return false;
+    const size_t beg = hd == 0 ? 0 : hd + 1, eol = text.find('\n', beg);
+    const std::string line = text.substr(beg, eol == std::string::npos ? std::string::npos : eol - beg);
+    size_t k = 0;
+    while (k <= line.size()) {
+        const size_t tab = line.find('\t', k);
+        const std::string field = line.substr(k, tab == std::string::npos ? std::string::npos : tab - k);
+        if (field == "SO:coordinate") return true;
+        if (tab == std::string::npos) break;
+        k = tab + 1;
+    }
+    return false;
+}
+
+// The virtual position behind the header's last byte: the first record's chunk start (the header is read on the host at
+// open; this walks the BGZF framing of its blocks only).  header_bytes = decompressed bytes in front of the first record.
+int header_end_voffset(ngsq_bam *b, uint64_t header_bytes, uint64_t *out) {
+    FILE *f = fopen(b->path.c_str(), "rb");
+    if (!f) return ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "%s: cannot open", b->path.c_str());
+    uint64_t coff = 0, total = 0;
+    int rc = NGSQ_OK;
+    std::vector<uint8_t> buf;
+    for (;;) {
+        uint8_t hd[18];
+        if (fseeko(f, (off_t)coff, SEEK_SET) != 0 || fread(hd, 1, 18, f) != 18) {
+            rc = ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "%s: the file ends inside the BAM header", b->path.c_str());
+            break;
+        }
+        const uint32_t xlen = bgzf_rd16(hd + 10);
+        buf.resize(12 + (size_t)xlen + 8);
+        memcpy(buf.data(), hd, 18);
+        if (fseeko(f, (off_t)coff, SEEK_SET) != 0 || fread(buf.data(), 1, 12 + (size_t)xlen, f) != 12 + (size_t)xlen) {
+            rc = ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "%s: truncated BGZF block in the header", b->path.c_str());
+            break;
+        }
+        // BSIZE from the extra field, then ISIZE from the block's trailer
+        uint32_t bsize = 0;
+        for (size_t q = 12; q + 4 <= 12 + (size_t)xlen;) {
+            const uint32_t slen = bgzf_rd16(buf.data() + q + 2);
+            if (buf[q] == 'B' && buf[q + 1] == 'C' && slen == 2) bsize = bgzf_rd16(buf.data() + q + 4) + 1;
+            q += 4 + slen;
+        }
+        uint8_t tr[4];
+        if (!bsize || fseeko(f, (off_t)(coff + bsize - 4), SEEK_SET) != 0 || fread(tr, 1, 4, f) != 4) {
+            rc = ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "%s: corrupt BGZF block in the header", b->path.c_str());
+            break;
+        }
+        const uint64_t isize = bgzf_rd32(tr);
+        if (header_bytes > total && header_bytes <= total + isize) { // the header's last byte is in this block
+            *out = header_bytes == total + isize ? (coff + bsize) << 16 : coff << 16 | (header_bytes - total);
+            break;
+        }
+        total += isize;
+        coff += bsize;
+    }
+    fclose(f);
+    return rc;
+}
+
+void put32(std::vector<uint8_t> &v, uint32_t x) {
+    for (int k = 0; k < 4; k++) v.push_back((uint8_t)(x >> (8 * k)));
+}
+void put64(std::vector<uint8_t> &v, uint64_t x) {
+    for (int k = 0; k < 8; k++) v.push_back((uint8_t)(x >> (8 * k)));
+}
+
+constexpr uint64_t BATCH_RECORDS = (uint64_t)1 << 22;
+constexpr uint32_t META_BIN = 37450;      // samtools' metadata pseudo-bin
+constexpr uint32_t LIN_SLACK = 64;        // windows kept beyond @SQ LN: records may reach 1 Mbp past the sequence's end
+constexpr uint32_t LIN_MAX = 1u << 15;    // 2^29 / 16384: the windows of the BAI's coordinate range
+
+} // namespace
+
+extern "C" int ngsq_bam_build_index(ngsq_bam *b, ngsq_ctx *c, const char *bai_path, ngsq_index_report *out) {
+    if (!b || !c || !bai_path) return ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "null argument");
+    if (out) memset(out, 0, sizeof *out);
+    if (b->dev || b->host_mode || b->n_read)
+        return ngsq_bam_fail(NGSQ_ERR_STATE, "%s: an index is built from a reader no record has been read from", b->path.c_str());
+    struct stat sb;
+    if (stat(bai_path, &sb) == 0)
+        return ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT,
+                             "refusing to overwrite existing index file: %s. Please delete and rerun if you'd like to replace it.", bai_path);
+    if (!header_coordinate_sorted(b->header_text))
+        return ngsq_bam_fail(NGSQ_ERR_UNSORTED, "the input BAM must be coordinate-sorted to be indexed");
+    const double t0 = now_ms();
+    uint64_t hdr_endv = 0;
+    {
+        const int rc = header_end_voffset(b, b->header_bytes, &hdr_endv);
+        if (rc) return rc;
+    }
+    IHIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const uint32_t n_refs = (uint32_t)b->ref_lens.size();
+    // ---- device state: linear windows per sequence, unmapped counts, the carry, the run list
+    std::vector<uint64_t> lin_base(n_refs + 1, 0);
+    std::vector<uint32_t> lin_cap(n_refs, 0);
+    for (uint32_t r = 0; r < n_refs; r++) {
+        lin_cap[r] = std::min<uint32_t>((uint32_t)(((uint64_t)b->ref_lens[r] + 16383) >> 14) + LIN_SLACK, LIN_MAX);
+        lin_base[r + 1] = lin_base[r] + lin_cap[r];
+    }
+    const uint64_t n_win = lin_base[n_refs];
+    // one upload of the setup words: [state | lin_base | lin_cap]
+    const size_t state_words = (sizeof(BaiState) + 7) / 8;
+    std::vector<uint64_t> setup(state_words + n_refs + (n_refs + 1) / 2 + 1, 0);
+    {
+        BaiState s0;
+        memset(&s0, 0, sizeof s0);
+        s0.carry[0].endv = hdr_endv;
+        s0.bad_order = ~0ull;
+        s0.bad_limit = ~0ull;
+        memcpy(setup.data(), &s0, sizeof s0);
+        memcpy(setup.data() + state_words, lin_base.data(), n_refs * sizeof(uint64_t));
+        memcpy(setup.data() + state_words + n_refs, lin_cap.data(), n_refs * sizeof(uint32_t));
+    }
+    DevArr<uint64_t> d_setup;
+    DevArr<unsigned long long> d_lin, d_unm;
+    DevArr<uint64_t> d_flag, d_scan;
+    DevArr<BaiRun> d_tmp, d_runs;
+    IHIP(d_setup.reserve(setup.size()));
+    IHIP(d_lin.reserve(n_win + 1));
+    IHIP(d_unm.reserve(n_refs + 1));
+    IHIP(hipMemcpyAsync(d_setup.p, setup.data(), setup.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    IHIP(hipMemsetAsync(d_lin.p, 0xFF, (n_win + 1) * sizeof(unsigned long long), st));
+    IHIP(hipMemsetAsync(d_unm.p, 0, (n_refs + 1) * sizeof(unsigned long long), st));
+    BaiState *d_state = reinterpret_cast<BaiState *>(d_setup.p);
+    BaiLinear L;
+    L.lin = d_lin.p;
+    L.lin_base = d_setup.p + state_words;
+    L.lin_cap = reinterpret_cast<const uint32_t *>(d_setup.p + state_words + n_refs);
+    L.unmapped = d_unm.p;
+    L.n_refs = n_refs;
+    // results the host reads: [count of runs | state words | unmapped | n_intv] in mapped pinned memory
+    Pinned pin;
+    const size_t pin_words = 8 + BAI_HOST_STATE_WORDS + 2 * (size_t)n_refs;
+    {
+        void *h = nullptr, *dv = nullptr;
+        IHIP(hipHostMalloc(&h, pin_words * sizeof(unsigned long long), hipHostMallocMapped));
+        pin.h = static_cast<unsigned long long *>(h);
+        memset(pin.h, 0, pin_words * sizeof(unsigned long long));
+        IHIP(hipHostGetDevicePointer(&dv, h, 0));
+        pin.dev = static_cast<unsigned long long *>(dv);
+    }
+    unsigned long long *const host_count = pin.dev, *const host_fin = pin.dev + 8;
+    hipEvent_t ev = nullptr;
+    IHIP(pool_event_get(&ev));
+    struct EvPut {
+        hipEvent_t e;
+        ~EvPut() { pool_event_put(e); }
+    } ev_put{ev};
+    // ---- the scan: every batch of the device ingest, in file order
+    uint64_t records = 0, runs = 0;
+    uint32_t parity = 0;
+    bool pending = false; // a gather has been queued whose count the host has not read yet
+    for (;;) {
+        ngsq_batch bt;
+        const int rc = ngsq_bam_next_batch_device(b, c, BATCH_RECORDS, &bt);
+        if (rc) return rc;
+        if (pending) { // (the ingest has waited for its own kernels, queued behind that gather: this returns at once)
+            IHIP(hipEventSynchronize(ev));
+            runs = pin.h[0];
+            pending = false;
+        }
+        const uint64_t n = bt.n_records;
+        if (!n) break;
+        BaiOrigin o;
+        {
+            const int rc2 = bam_device_batch_origin(b, &o);
+            if (rc2) return rc2;
+        }
+        IHIP(d_flag.reserve(n + 1));
+        IHIP(d_tmp.reserve(n));
+        IHIP(d_runs.reserve(runs + n, st, true));
+        size_t tmp_bytes = 0;
+        IHIP(launch_exclusive_scan_u64(d_flag.p, n + 1, nullptr, &tmp_bytes, st));
+        IHIP(d_scan.reserve(tmp_bytes / sizeof(uint64_t) + 1));
+        {
+            KernelTimer kt(c, K_REC_INDEX, n * 16);
+            IHIP(launch_bai_records(bt, o, d_state, parity, L, d_flag.p, d_tmp.p, st));
+            tmp_bytes = d_scan.cap * sizeof(uint64_t);
+            IHIP(launch_exclusive_scan_u64(d_flag.p, n + 1, d_scan.p, &tmp_bytes, st));
+            IHIP(launch_bai_gather(d_flag.p, d_tmp.p, n, d_runs.p, runs, host_count, st));
+        }
+        IHIP(hipEventRecord(ev, st));
+        pending = true;
+        parity ^= 1u;
+        records += n;
+    }
+    // ---- the end: linear gaps filled on the device, then the run list and the windows to the host
+    IHIP(launch_bai_finish(L, d_state, parity, host_fin, st));
+    std::vector<BaiRun> R(runs);
+    std::vector<unsigned long long> lin(n_win);
+    if (runs) IHIP(hipMemcpyAsync(R.data(), d_runs.p, runs * sizeof(BaiRun), hipMemcpyDeviceToHost, st));
+    if (n_win) IHIP(hipMemcpyAsync(lin.data(), d_lin.p, n_win * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    IHIP(hipStreamSynchronize(st));
+    const unsigned long long *fin = pin.h + 8;
+    if (fin[0] != ~0ull)
+        return ngsq_bam_fail(NGSQ_ERR_UNSORTED, "%s: record %llu (0-based) is out of coordinate order: the input BAM must be coordinate-sorted to be indexed",
+                             b->path.c_str(), fin[0]);
+    if (fin[1] != ~0ull)
+        return ngsq_bam_fail(NGSQ_ERR_LIMIT, "%s: record %llu (0-based) cannot be held by a BAI: its sequence id is out of range, or it reaches "
+                             "beyond position 2^29 or more than 1 Mbp beyond its @SQ LN",
+                             b->path.c_str(), fin[1]);
+    const uint64_t final_end = fin[2];
+    const unsigned long long *unmapped = fin + BAI_HOST_STATE_WORDS, *n_intv = unmapped + n_refs;
+    const double t1 = now_ms();
+    // ---- the file (SAM/BAM specification 5.2): per sequence its bins in ascending order, each with its runs in file order
+    // (one chunk each: two runs of one bin are never adjacent), the pseudo-bin, the linear index; then n_no_coor
+    std::vector<uint8_t> idx;
+    idx.reserve(16 + runs * 20 + n_win * 8 + n_refs * 64);
+    idx.insert(idx.end(), {'B', 'A', 'I', 1});
+    put32(idx, n_refs);
+    std::vector<uint32_t> cnt(META_BIN, 0), at(META_BIN, 0), touched, order;
+    uint64_t k = 0, n_bins = 0;
+    for (uint32_t r = 0; r < n_refs; r++) {
+        while (k < runs && R[k].ref >= 0 && (uint32_t)R[k].ref < r) k++; // (sorted: nothing is skipped)
+        const uint64_t a = k;
+        while (k < runs && R[k].ref == (int32_t)r) k++;
+        const uint64_t e = k;
+        if (a == e) {
+            put32(idx, 0);
+        } else {
+            touched.clear();
+            for (uint64_t q = a; q < e; q++)
+                if (cnt[R[q].bin]++ == 0) touched.push_back(R[q].bin);
+            std::sort(touched.begin(), touched.end());
+            uint32_t acc = 0;
+            for (uint32_t bn : touched) {
+                at[bn] = acc;
+                acc += cnt[bn];
+            }
+            order.resize(acc);
+            for (uint64_t q = a; q < e; q++) order[at[R[q].bin]++] = (uint32_t)(q - a);
+            put32(idx, (uint32_t)touched.size() + 1);
+            size_t o = 0;
+            for (uint32_t bn : touched) {
+                put32(idx, bn);
+                put32(idx, cnt[bn]);
+                for (uint32_t j = 0; j < cnt[bn]; j++, o++) {
+                    const uint64_t q = a + order[o];
+                    put64(idx, R[q].start);
+                    put64(idx, q + 1 < runs ? R[q + 1].start : final_end);
+                }
+                cnt[bn] = 0;
+            }
+            n_bins += touched.size();
+            const uint64_t placed = (e < runs ? R[e].rec : records) - R[a].rec;
+            put32(idx, META_BIN);
+            put32(idx, 2);
+            put64(idx, R[a].start);
+            put64(idx, e < runs ? R[e].start : final_end);
+            put64(idx, placed - unmapped[r]);
+            put64(idx, unmapped[r]);
+        }
+        const uint32_t ni = (uint32_t)n_intv[r];
+        put32(idx, ni);
+        for (uint32_t w = 0; w < ni; w++) put64(idx, lin[lin_base[r] + w]);
+    }
+    uint64_t n_no_coor = 0;
+    if (runs && R[runs - 1].ref < 0) n_no_coor = records - R[runs - 1].rec;
+    put64(idx, n_no_coor);
+    // written beside its place and renamed: an error leaves nothing at bai_path
+    std::string tmp = std::string(bai_path) + ".XXXXXX";
+    const int fd = mkstemp(&tmp[0]);
+    if (fd < 0) return ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "creating BAM index output file: cannot create %s", tmp.c_str());
+    size_t done = 0;
+    while (done < idx.size()) {
+        const ssize_t w = write(fd, idx.data() + done, idx.size() - done);
+        if (w <= 0) break;
+        done += (size_t)w;
+    }
+    const bool written = done == idx.size() && fchmod(fd, 0644) == 0;
+    const bool ok = close(fd) == 0 && written;
+    if (!ok || rename(tmp.c_str(), bai_path) != 0) {
+        unlink(tmp.c_str());
+        return ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "writing BAM index: cannot write %s", bai_path);
+    }
+    if (out) {
+        out->records = records;
+        out->n_no_coor = n_no_coor;
+        out->runs = runs;
+        out->bins = n_bins;
+        out->scan_ms = t1 - t0;
+        out->write_ms = now_ms() - t1;
+    }
+    return NGSQ_OK;
+}

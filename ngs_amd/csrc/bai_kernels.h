@@ -1,0 +1,75 @@
+// bai_kernels.h -- `ngs index` on the device: the BAI of a coordinate-sorted BAM built from the
+// batches of the device ingest.  Launchers only; bai_kernel.hip has the kernels, bai.cpp the driver and the file writer.
+#pragma once
+
+#include <hip/hip_runtime_api.h>
+#include <stdint.h>
+
+#include "ingest_kernels.h"
+
+struct ngsq_bam;
+
+namespace ngsq {
+
+// where the records of the batch the device ingest handed out last came from: what a record's chunk positions are drawn
+// from (the position behind a record's last byte, htslib's rule: DESIGN.md section 12.1)
+struct BaiOrigin {
+    const uint8_t *raw;      // the ingest's view of the inflated stream
+    const uint64_t *rec_off; // [n] view offset of every record of the batch
+    const BgzfBlock *blocks; // the chunk's block table, out_off relative to the chunk's first byte (view offset - carry)
+    const uint64_t *coff;    // [n_blocks] file offset of every block
+    uint32_t n_blocks;
+    uint64_t carry;          // view bytes in front of the chunk's first byte
+    uint64_t next_coff;      // file offset behind the chunk's last block
+};
+// bam_device_reader.cpp: the origin of the last batch of ngsq_bam_next_batch_device (valid until the next call)
+int bam_device_batch_origin(ngsq_bam *b, BaiOrigin *out);
+
+// What one record passes on to the next one, across blocks and batches.
+struct BaiCarry {
+    int32_t ref, pos;
+    uint32_t bin, w1;    // bin; last 16 kb window it overlaps
+    uint32_t placed;     // ref >= 0 and pos >= 0
+    uint32_t has;        // a record has been seen
+    uint64_t endv;       // virtual position behind the record (for the first record: behind the header)
+};
+
+// one run of records of the same (sequence, bin), in file order: exactly one chunk
+struct BaiRun {
+    uint64_t start; // chunk start: the position behind the record in front of its first record
+    uint64_t rec;   // index of its first record in the file
+    int32_t ref;    // -1: the unplaced records at the end of the file
+    uint32_t bin;
+};
+
+// device words of one index build (zeroed / set by bai.cpp before the first batch)
+struct BaiState {
+    BaiCarry carry[2];          // batch k reads carry[k & 1] and writes carry[(k + 1) & 1]
+    unsigned long long bad_order; // smallest index of a record that breaks the coordinate order, ~0: none
+    unsigned long long bad_limit; // smallest index of a record the BAI cannot hold (sequence id, or beyond the windows kept), ~0: none
+};
+
+// per-sequence linear index: windows [lin_base[r], lin_base[r] + lin_cap[r]) of `lin`, ~0 = no record overlaps the window
+struct BaiLinear {
+    unsigned long long *lin;
+    const uint64_t *lin_base;
+    const uint32_t *lin_cap;
+    unsigned long long *unmapped; // [n_refs] placed records with flag 0x4
+    uint32_t n_refs;
+};
+
+// One pass over a batch: reference span, bin and the order check of every record, the linear windows it is the first to
+// overlap, its unmapped flag; run_flag[i] = 1 where a run starts (and run_flag[n] = 0), tmp_runs[i] its entry.
+hipError_t launch_bai_records(const ngsq_batch &b, const BaiOrigin &o, BaiState *state, uint32_t parity, const BaiLinear &lin,
+                              uint64_t *run_flag, BaiRun *tmp_runs, hipStream_t s);
+// after the exclusive scan of run_flag: the batch's runs behind the `base` runs already listed; host_count (pinned, device
+// address) receives base + the batch's runs
+hipError_t launch_bai_gather(const uint64_t *run_off, const BaiRun *tmp_runs, uint64_t n, BaiRun *runs, uint64_t base,
+                             unsigned long long *host_count, hipStream_t s);
+// End of the file: every sequence's empty windows take the value in front of them (0 before its first record);
+// n_intv[r] = last window a record overlaps + 1.  host (pinned, device address): [state words | unmapped[n_refs] | n_intv[n_refs]]
+// with the state words = bad_order, bad_limit, the final carry's endv.
+hipError_t launch_bai_finish(const BaiLinear &lin, const BaiState *state, uint32_t parity, unsigned long long *host, hipStream_t s);
+constexpr uint32_t BAI_HOST_STATE_WORDS = 4;
+
+} // namespace ngsq

@@ -24,6 +24,7 @@
 
 #include "../../include/ngsq_bam.h"
 #include "bam_reader.h"
+#include "bai_kernels.h"
 #include "bgzf.h"
 #include "context.h"
 #include "ingest_kernels.h"
@@ -297,6 +298,7 @@ struct DeviceIngest {
     bool last_chunk = false;      // the chunk being handed out is the range's last
     ngsq_bam_ingest_stats stats{}; // ngsq_bam_device_stats
     uint64_t chunk_first_record = 0; // records handed out before the current chunk (for the message of an invalid record)
+    const uint64_t *batch_rec = nullptr; // view offsets of the records of the last batch handed out (bam_device_batch_origin)
     ~DeviceIngest() {
         {
             std::lock_guard<std::mutex> g(mu);
@@ -1354,6 +1356,23 @@ extern "C" int ngsq_bam_shard_end(ngsq_bam *b, ngsq_bam_shard_info *out) {
     return ngsq_bam_shard_peek(b, out, &assumed);
 }
 
+namespace ngsq {
+int bam_device_batch_origin(ngsq_bam *b, BaiOrigin *out) {
+    if (!b || !out) return ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "null argument");
+    const DeviceIngest *d = b->dev;
+    if (!d || !d->batch_rec) return ngsq_bam_fail(NGSQ_ERR_STATE, "%s: no device batch handed out", b->path.c_str());
+    const DeviceIngest::Pending &p = d->pend[d->cur_slot];
+    out->raw = d->raw;
+    out->rec_off = d->batch_rec;
+    out->blocks = d->d_blocks_s[d->cur_slot].p;
+    out->coff = d->d_coff_s[d->cur_slot].p;
+    out->n_blocks = (uint32_t)p.blocks.size();
+    out->carry = d->carry_len;
+    out->next_coff = p.next_coff;
+    return NGSQ_OK;
+}
+} // namespace ngsq
+
 extern "C" {
 
 int ngsq_bam_next_batch_device(ngsq_bam *b, ngsq_ctx *c, uint64_t max_records, ngsq_batch *out) {
@@ -1479,6 +1498,7 @@ int ngsq_bam_next_batch_device(ngsq_bam *b, ngsq_ctx *c, uint64_t max_records, n
         KernelTimer kt(d->ctx, K_REC_COLUMNS, 2 * (so + qo + co * 4));
         BHIP(launch_rec_var(d->raw, d->d_var_base.p, n, col, so, qo, st));
     }
+    d->batch_rec = rec;
     d->cursor += n;
     b->n_read += n;
     out->n_records = n;

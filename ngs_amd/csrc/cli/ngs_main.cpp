@@ -38,6 +38,7 @@
 
 #include "../../../include/ngsq.h"
 #include "../../../include/ngsq_bam.h"
+#include "../../../include/ngsq_index.h"
 #include "../../../include/ngsq_stage.h"
 #include "../../../include/ngsq_comm.h"
 #include "../../../include/ngsq_reference.h"
@@ -269,7 +270,90 @@ void usage() {
             "      --gene-feature-name <STRING>              GFF feature of a gene [default: gene]\n"
             "      --device <N> --batch-records <N> --threads <N> --gc-seed <N> --ingest host|device   (additive, this build)\n"
             "      --coverage auto|stream|array   Coverage finished while sorted records stream by / on depth arrays (additive)\n"
-            "      --gpus <N>                  One worker per GPU over BGZF block ranges of the file, one RCCL exchange (additive)\n");
+            "      --gpus <N>                  One worker per GPU over BGZF block ranges of the file, one RCCL exchange (additive)\n\n"
+            "       ngs [-q|-v] index [--device <N>] <BAM>   Write <BAM>.bai, built on the GPU (BAM only in this build)\n");
+}
+
+// ---- `ngs index` (src/index/command.rs:26-46, src/index/bam.rs:39-109) -------------------------
+// argv[at] is "index".  Exit 0 on success, 1 on every error (anyhow::bail! in the reference).
+int index_main(int argc, char **argv, int at) {
+    std::string src;
+    int device = 0, n_pos = 0;
+    for (int i = at + 1; i < argc; i++) {
+        const std::string s = argv[i];
+        if (s == "-q" || s == "--quiet") g_level = 0;
+        else if (s == "-v" || s == "--verbose") g_level = 3;
+        else if (s == "-h" || s == "--help") {
+            fprintf(stderr, "Usage: ngs index [--device <N>] <BAM/CRAM/FASTA>\n\n"
+                            "Arguments:\n  <BAM/CRAM/FASTA>  Path to the file to index (BAM only in this build)\n\n"
+                            "Options:\n      --device <N>  GPU the index is built on (additive, this build) [default: 0]\n");
+            return 0;
+        } else if (s == "--device") {
+            if (i + 1 >= argc) bail("a value is required for '--device <N>' but none was supplied");
+            device = atoi(argv[++i]);
+        } else if (!s.empty() && s[0] == '-') bail("unexpected argument '" + s + "' found");
+        else {
+            src = s;
+            n_pos++;
+        }
+    }
+    if (n_pos == 0) bail("the following required arguments were not provided: <BAM/CRAM/FASTA>");
+    if (n_pos > 1) bail("unexpected argument found: `ngs index` takes one file");
+    // BioinformaticsFileFormat::try_detect by extension (utils/formats.rs), as for qc
+    const std::string format = detect_format(src);
+    if (format.empty()) bail("Not able to determine bioinformatics file type for path: " + src);
+    if (format == "CRAM" || format == "FASTA")
+        bail(format + " files are indexed by the reference `ngs index` but not by this build, which indexes BAM files only");
+    if (format != "BAM")
+        bail(format + " files are not supported by this command. This may be because we haven't supported this file format yet or "
+                      "because it does not make sense to index a file of this kind. If you believe this format should be supported, "
+                      "please search for and upvote the related issue on Github (or file a new one).");
+    // (1) open and parse (IndexCheck::None), (2) refuse an existing index, (3) require SO:coordinate -- before any GPU work
+    ngsq_bam *bam = nullptr;
+    if (ngsq_bam_open(src.c_str(), 0, &bam) != NGSQ_OK) bail(ngsq_bam_last_error());
+    const std::string bai = src + ".bai";
+    struct stat sb;
+    if (stat(bai.c_str(), &sb) == 0)
+        bail("refusing to overwrite existing index file: " + bai + ". Please delete and rerun if you'd like to replace it.");
+    {
+        uint64_t hl = 0;
+        const char *ht = ngsq_bam_header_text(bam, &hl);
+        const std::string text(ht ? ht : "", ht ? hl : 0);
+        const size_t hd = text.rfind("@HD", 0) == 0 ? 0 : text.find("\n@HD");
+        bool sorted = false;
+        if (hd != std::string::npos) {
+            const size_t beg = hd ? hd + 1 : 0, eol = text.find('\n', beg);
+            const std::string line = "\t" + text.substr(beg, eol == std::string::npos ? std::string::npos : eol - beg) + "\t";
+            sorted = line.find("\tSO:coordinate\t") != std::string::npos;
+        }
+        if (!sorted) bail("the input BAM must be coordinate-sorted to be indexed");
+    }
+    // (5) the index: the device ingest and the index kernels on one GPU; a context without facets
+    const uint32_t n_refs = ngsq_bam_n_refs(bam);
+    std::vector<uint32_t> lens(n_refs);
+    for (uint32_t r = 0; r < n_refs; r++) lens[r] = ngsq_bam_ref_len(bam, r);
+    ngsq_config cfg{};
+    cfg.struct_size = sizeof cfg;
+    cfg.facets = 0;
+    cfg.device = device;
+    cfg.n_refs = n_refs;
+    cfg.ref_len = lens.data();
+    ngsq_ctx *ctx = nullptr;
+    if (ngsq_create(&cfg, &ctx) != NGSQ_OK) bail(ngsq_last_global_error());
+    ngsq_index_report rep{};
+    if (ngsq_bam_build_index(bam, ctx, bai.c_str(), &rep) != NGSQ_OK) {
+        const std::string msg = ngsq_bam_last_error();
+        ngsq_destroy(ctx);
+        ngsq_bam_close(bam);
+        bail(msg);
+    }
+    if (g_level >= 3)
+        fprintf(stderr, "[ngs] index: %llu records (%llu without coordinates), %llu chunks in %llu bins; scan %.1f ms, write %.1f ms\n",
+                (unsigned long long)rep.records, (unsigned long long)rep.n_no_coor, (unsigned long long)rep.runs,
+                (unsigned long long)rep.bins, rep.scan_ms, rep.write_ms);
+    ngsq_destroy(ctx);
+    ngsq_bam_close(bam);
+    return 0;
 }
 
 #define CHECK(ctx, expr)                                                                                   \
@@ -289,6 +373,14 @@ static void milestone(const char *what) {
 
 int main(int argc, char **argv) {
     milestone("main");
+    { // `ngs [-q|-v] index ...`: its own arguments (the qc parser below never sees them)
+        int k = 1;
+        while (k < argc && (!strcmp(argv[k], "-q") || !strcmp(argv[k], "--quiet") || !strcmp(argv[k], "-v") || !strcmp(argv[k], "--verbose"))) {
+            g_level = argv[k][1] == 'q' || !strcmp(argv[k], "--quiet") ? 0 : 3;
+            k++;
+        }
+        if (k < argc && !strcmp(argv[k], "index")) return index_main(argc, argv, k);
+    }
     Args a;
     std::vector<std::string> pos;
     bool saw_qc = false;

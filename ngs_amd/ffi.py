@@ -222,6 +222,13 @@ class IngestStats(C.Structure):
 
 ctx_p = C.c_void_p
 
+
+# ---- include/ngsq_index.h ---------------------------------------------------------------------
+class IndexReport(C.Structure):
+    _fields_ = [("records", C.c_uint64), ("n_no_coor", C.c_uint64), ("runs", C.c_uint64), ("bins", C.c_uint64),
+                ("scan_ms", C.c_double), ("write_ms", C.c_double)]
+
+
 # ---- include/ngsq_comm.h ----------------------------------------------------------------------
 COMM_ID_BYTES = 128
 COMM_MAX_WORLD = 64
@@ -364,6 +371,8 @@ PROTOTYPES = {
     "ngsq_bam_device_stats": (C.c_int, [C.c_void_p, C.POINTER(IngestStats)]),
     "ngsq_bam_shard_begin": (C.c_int, [C.c_void_p, ctx_p, C.c_uint32, C.c_uint32, C.c_uint64]),
     "ngsq_bam_shard_end": (C.c_int, [C.c_void_p, C.POINTER(ShardInfo)]),
+    # include/ngsq_index.h
+    "ngsq_bam_build_index": (C.c_int, [C.c_void_p, ctx_p, C.c_char_p, C.POINTER(IndexReport)]),
     "ngsq_bgzf_inflate_device": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p, C.c_int]),
     # include/ngsq_comm.h
     "ngsq_comm_last_error": (C.c_char_p, [comm_p]),

@@ -501,3 +501,32 @@ class QcContext:
     def state_upload(self, which: int, a: np.ndarray):
         a = np.ascontiguousarray(a)
         _check(self.lib.ngsq_state_upload(self._ctx, which, a.ctypes.data, a.nbytes), self._ctx, self.lib)
+
+
+def build_bam_index(path: str, device: int = 0, bai_path: Optional[str] = None, lib=None) -> Dict[str, float]:
+    """`ngs index` in process (include/ngsq_index.h): write the BAI of the coordinate-sorted BAM `path` to bai_path
+    (default "<path>.bai"), built on GPU `device` from the device ingest.  Returns the report; NgsqError on any refusal."""
+    lib = lib or ffi.load_library()
+    bam = C.c_void_p()
+    rc = lib.ngsq_bam_open(path.encode(), 0, C.byref(bam))
+    if rc != ffi.OK:
+        raise NgsqError(rc, (lib.ngsq_bam_last_error() or b"").decode("utf-8", "replace"))
+    try:
+        n_refs = lib.ngsq_bam_n_refs(bam)
+        lens = np.array([lib.ngsq_bam_ref_len(bam, r) for r in range(n_refs)], dtype=np.uint32)
+        cfg = ffi.Config()
+        cfg.struct_size = C.sizeof(ffi.Config)
+        cfg.facets, cfg.device, cfg.n_refs = 0, device, n_refs
+        cfg.ref_len = lens.ctypes.data_as(ffi.u32p)
+        ctx = ffi.ctx_p()
+        _check(lib.ngsq_create(C.byref(cfg), C.byref(ctx)), None, lib)
+        try:
+            rep = ffi.IndexReport()
+            rc = lib.ngsq_bam_build_index(bam, ctx, (bai_path or path + ".bai").encode(), C.byref(rep))
+            if rc != ffi.OK:
+                raise NgsqError(rc, (lib.ngsq_bam_last_error() or b"").decode("utf-8", "replace"))
+            return {k: getattr(rep, k) for k, _ in ffi.IndexReport._fields_}
+        finally:
+            lib.ngsq_destroy(ctx)
+    finally:
+        lib.ngsq_bam_close(bam)
