@@ -14,11 +14,12 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libngsq.so")
 SOURCES = ["kernels.hip", "qual_kernel.hip", "fields_kernel.hip", "cov_scan.hip", "cov_stream.hip", "synth.hip", "bgzf_inflate.hip",
            "bam_device.hip", "features_kernel.hip", "edits_kernel.hip", "exchange_kernels.hip", "comm.cpp", "exchange.cpp", "mem_pool.cpp", "context.cpp", "stager.cpp", "results.cpp", "bam_reader.cpp", "bam_device_reader.cpp", "synth_bam.cpp",
-           "reference.cpp", "reference_kernels.hip", "bai_kernel.hip", "bai.cpp"]
+           "reference.cpp", "reference_kernels.hip", "bai_kernel.hip", "bai.cpp",
+           "sam_kernel.hip", "sam.cpp"]
 HEADERS = ["kernels.h", "context.h", "comm.h", "mem_pool.h", "ingest_kernels.h", "bgzf.h", "reference_kernels.h", "../../include/ngsq.h",
            "../../include/ngsq_reference.h", "../../include/ngsq_comm.h",
            "../../include/ngsq_shared.h", "../../include/ngsq_synth.h", "../../include/ngsq_bam.h", "../../include/ngsq_stage.h",
-           "bai_kernels.h", "../../include/ngsq_index.h"]
+           "bai_kernels.h", "../../include/ngsq_index.h", "sam_kernels.h", "../../include/ngsq_sam.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-result", "-fno-gpu-rdc"]
 FLAGS += os.environ.get("NGSQ_EXTRA_FLAGS", "").split()  # extra compiler flags for a local build, e.g. -save-temps (use --force)
 OBJ_DIR = os.path.join(HERE, "_obj")  # per-source objects (git-ignored): only changed sources recompile

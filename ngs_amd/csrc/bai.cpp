@@ -236,7 +236,7 @@ extern "C" int ngsq_bam_build_index(ngsq_bam *b, ngsq_ctx *c, const char *bai_pa
         }
         const uint64_t n = bt.n_records;
         if (!n) break;
-        BaiOrigin o;
+        BatchOrigin o;
         {
             const int rc2 = bam_device_batch_origin(b, &o);
             if (rc2) return rc2;

@@ -56,7 +56,7 @@ __device__ inline RecInfo bai_info(const ngsq_batch &b, uint64_t i) {
 
 // The virtual position behind the byte in front of view offset e (e > o.carry: in this chunk): inside the byte's block,
 // or -- the block's last byte -- the start of the block behind it, empty or not (htslib's reader)
-__device__ inline uint64_t bai_pos_after(const BaiOrigin &o, uint64_t e) {
+__device__ inline uint64_t bai_pos_after(const BatchOrigin &o, uint64_t e) {
     const uint64_t u = e - o.carry;
     uint32_t lo = 0, hi = o.n_blocks; // the last block with out_off <= u - 1: the one that holds that byte
     while (hi - lo > 1) {
@@ -75,7 +75,7 @@ __device__ inline uint32_t ld32u(const uint8_t *p) {
     return v;
 }
 
-__global__ __launch_bounds__(BT) void k_bai_records(ngsq_batch b, BaiOrigin o, BaiState *__restrict__ st, uint32_t parity, BaiLinear L,
+__global__ __launch_bounds__(BT) void k_bai_records(ngsq_batch b, BatchOrigin o, BaiState *__restrict__ st, uint32_t parity, BaiLinear L,
                                                     uint64_t *__restrict__ run_flag, BaiRun *__restrict__ tmp) {
     __shared__ int32_t s_ref[BT], s_pos[BT];
     __shared__ uint32_t s_bin[BT], s_w1[BT], s_placed[BT];
@@ -239,7 +239,7 @@ __global__ __launch_bounds__(BT) void k_bai_finish(BaiLinear L, const BaiState *
 
 } // namespace
 
-hipError_t launch_bai_records(const ngsq_batch &b, const BaiOrigin &o, BaiState *state, uint32_t parity, const BaiLinear &lin,
+hipError_t launch_bai_records(const ngsq_batch &b, const BatchOrigin &o, BaiState *state, uint32_t parity, const BaiLinear &lin,
                               uint64_t *run_flag, BaiRun *tmp_runs, hipStream_t s) {
     if (!b.n_records) return hipSuccess;
     const uint64_t blocks = (b.n_records + BT - 1) / BT;

@@ -7,23 +7,7 @@
 
 #include "ingest_kernels.h"
 
-struct ngsq_bam;
-
 namespace ngsq {
-
-// where the records of the batch the device ingest handed out last came from: what a record's chunk positions are drawn
-// from (the position behind a record's last byte, htslib's rule: DESIGN.md section 12.1)
-struct BaiOrigin {
-    const uint8_t *raw;      // the ingest's view of the inflated stream
-    const uint64_t *rec_off; // [n] view offset of every record of the batch
-    const BgzfBlock *blocks; // the chunk's block table, out_off relative to the chunk's first byte (view offset - carry)
-    const uint64_t *coff;    // [n_blocks] file offset of every block
-    uint32_t n_blocks;
-    uint64_t carry;          // view bytes in front of the chunk's first byte
-    uint64_t next_coff;      // file offset behind the chunk's last block
-};
-// bam_device_reader.cpp: the origin of the last batch of ngsq_bam_next_batch_device (valid until the next call)
-int bam_device_batch_origin(ngsq_bam *b, BaiOrigin *out);
 
 // What one record passes on to the next one, across blocks and batches.
 struct BaiCarry {
@@ -60,7 +44,7 @@ struct BaiLinear {
 
 // One pass over a batch: reference span, bin and the order check of every record, the linear windows it is the first to
 // overlap, its unmapped flag; run_flag[i] = 1 where a run starts (and run_flag[n] = 0), tmp_runs[i] its entry.
-hipError_t launch_bai_records(const ngsq_batch &b, const BaiOrigin &o, BaiState *state, uint32_t parity, const BaiLinear &lin,
+hipError_t launch_bai_records(const ngsq_batch &b, const BatchOrigin &o, BaiState *state, uint32_t parity, const BaiLinear &lin,
                               uint64_t *run_flag, BaiRun *tmp_runs, hipStream_t s);
 // after the exclusive scan of run_flag: the batch's runs behind the `base` runs already listed; host_count (pinned, device
 // address) receives base + the batch's runs

@@ -1357,7 +1357,7 @@ extern "C" int ngsq_bam_shard_end(ngsq_bam *b, ngsq_bam_shard_info *out) {
 }
 
 namespace ngsq {
-int bam_device_batch_origin(ngsq_bam *b, BaiOrigin *out) {
+int bam_device_batch_origin(ngsq_bam *b, BatchOrigin *out) {
     if (!b || !out) return ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "null argument");
     const DeviceIngest *d = b->dev;
     if (!d || !d->batch_rec) return ngsq_bam_fail(NGSQ_ERR_STATE, "%s: no device batch handed out", b->path.c_str());

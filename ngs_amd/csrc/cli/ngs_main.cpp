@@ -11,6 +11,7 @@
 // GPU, each ingesting its BGZF block range of the file on its own device, one ngsq_exchange
 // (include/ngsq_comm.h; RCCL over xGMI) before the teardown, rank 0 writes the JSON.
 // Not built (out of scope this round): the other subcommands.
+#include <fcntl.h>
 #include <poll.h>
 #include <signal.h>
 #include <spawn.h>
@@ -21,6 +22,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cerrno>
 #include <charconv>
 #include <chrono>
 #include <cstdarg>
@@ -39,6 +41,7 @@
 #include "../../../include/ngsq.h"
 #include "../../../include/ngsq_bam.h"
 #include "../../../include/ngsq_index.h"
+#include "../../../include/ngsq_sam.h"
 #include "../../../include/ngsq_stage.h"
 #include "../../../include/ngsq_comm.h"
 #include "../../../include/ngsq_reference.h"
@@ -271,7 +274,9 @@ void usage() {
             "      --device <N> --batch-records <N> --threads <N> --gc-seed <N> --ingest host|device   (additive, this build)\n"
             "      --coverage auto|stream|array   Coverage finished while sorted records stream by / on depth arrays (additive)\n"
             "      --gpus <N>                  One worker per GPU over BGZF block ranges of the file, one RCCL exchange (additive)\n\n"
-            "       ngs [-q|-v] index [--device <N>] <BAM>   Write <BAM>.bai, built on the GPU (BAM only in this build)\n");
+            "       ngs [-q|-v] index [--device <N>] <BAM>   Write <BAM>.bai, built on the GPU (BAM only in this build)\n"
+            "       ngs [-q|-v] convert [OPTIONS] <FROM> <TO>   Convert BAM to SAM, the text formatted on the GPU (BAM to SAM only in\n"
+            "                                                   this build)\n");
 }
 
 // ---- `ngs index` (src/index/command.rs:26-46, src/index/bam.rs:39-109) -------------------------
@@ -356,6 +361,118 @@ int index_main(int argc, char **argv, int at) {
     return 0;
 }
 
+// ---- `ngs convert` (src/convert/command.rs:26-172, src/convert/bam.rs:24-70) --------------------
+// argv[at] is "convert".  Exit 0 on success, 1 on every error (anyhow::bail! in the reference).
+int convert_main(int argc, char **argv, int at) {
+    std::vector<std::string> pos;
+    bool has_n = false, has_fasta = false; // (-r and -c take no part in BAM to SAM, as in the reference)
+    unsigned long long n = 0;
+    int device = 0;
+    for (int i = at + 1; i < argc; i++) {
+        const std::string s = argv[i];
+        auto val = [&](const char *name) -> std::string {
+            if (i + 1 >= argc) bail(std::string("a value is required for '") + name + "' but none was supplied");
+            return argv[++i];
+        };
+        if (s == "-q" || s == "--quiet") g_level = 0;
+        else if (s == "-v" || s == "--verbose") g_level = 3;
+        else if (s == "-h" || s == "--help") {
+            fprintf(stderr,
+                    "Usage: ngs convert [OPTIONS] <FROM> <TO>\n\n"
+                    "Arguments:\n"
+                    "  <FROM>  Path to the source file from which we are converting\n"
+                    "  <TO>    Path to the destination file to which we are converting\n\n"
+                    "Options:\n"
+                    "  -n, --num-records <USIZE>\n"
+                    "          Number of records to process before exiting the conversion\n"
+                    "  -r, --reference-fasta <REFERENCE_FASTA>\n"
+                    "          If available, the FASTA reference file used to generate the file\n"
+                    "  -c, --compression-strategy <COMPRESSION_STRATEGY>\n"
+                    "          [default: balanced] [possible values: best, balanced, fastest]\n"
+                    "      --device <N>\n"
+                    "          GPU the SAM text is formatted on (additive, this build) [default: 0]\n\n"
+                    "This build converts BAM to SAM only.\n");
+            return 0;
+        } else if (s == "-n" || s == "--num-records") {
+            const std::string v = val("--num-records <USIZE>");
+            char *e = nullptr;
+            errno = 0;
+            n = strtoull(v.c_str(), &e, 10);
+            if (v.empty() || *e || errno || v[0] == '-' || v[0] == '+')
+                bail("invalid value '" + v + "' for '--num-records <USIZE>': invalid digit found in string");
+            has_n = true;
+        } else if (s == "-r" || s == "--reference-fasta") {
+            (void)val("--reference-fasta <REFERENCE_FASTA>");
+            has_fasta = true;
+        } else if (s == "-c" || s == "--compression-strategy") {
+            const std::string v = val("--compression-strategy <COMPRESSION_STRATEGY>");
+            if (v != "best" && v != "balanced" && v != "fastest")
+                bail("invalid value '" + v + "' for '--compression-strategy <COMPRESSION_STRATEGY>' [possible values: best, balanced, fastest]");
+        } else if (s == "--device") {
+            device = atoi(val("--device <N>").c_str());
+        } else if (!s.empty() && s[0] == '-' && s != "-") bail("unexpected argument '" + s + "' found");
+        else pos.push_back(s);
+    }
+    if (pos.size() < 2) bail(pos.empty() ? "the following required arguments were not provided: <FROM> <TO>"
+                                         : "the following required arguments were not provided: <TO>");
+    if (pos.size() > 2) bail("unexpected argument '" + pos[2] + "' found");
+    const std::string &from = pos[0], &to = pos[1];
+    // BioinformaticsFileFormat::try_detect of <FROM>, then of <TO> (command.rs:63-82), with their contexts
+    const std::string ff = detect_format(from);
+    if (ff.empty()) bail("failed to detect from input filetype: " + from + ": Failed parsing of bioinformatics file format.");
+    const std::string tf = detect_format(to);
+    if (tf.empty()) bail("failed to deteect to input filetype: " + to + ": Failed parsing of bioinformatics file format.");
+    // the pairs the reference converts (command.rs:104-171)
+    const bool cram = (ff == "SAM" && tf == "CRAM") || (ff == "CRAM" && tf == "SAM") || (ff == "BAM" && tf == "CRAM") ||
+                      (ff == "CRAM" && tf == "BAM");
+    const bool reference_only = (ff == "SAM" && tf == "BAM") || (ff == "GFF" && tf == "Block-gzipped GFF") || cram;
+    if (cram && !has_fasta) bail("--reference-fasta is a required argument when converting to/from a CRAM file");
+    if (reference_only)
+        bail("Conversion from " + ff + " to " + tf + " is done by the reference `ngs convert` but not by this build, which converts BAM to SAM only");
+    if (!(ff == "BAM" && tf == "SAM")) bail("Conversion from " + ff + " to " + tf + " is not currently supported");
+    // to_sam_async: (1) open the BAM (IndexCheck::None), (2) create the SAM file, (3) the header, (4) every record
+    ngsq_bam *bam = nullptr;
+    if (ngsq_bam_open(from.c_str(), 0, &bam) != NGSQ_OK) bail(std::string("opening BAM input file: ") + ngsq_bam_last_error());
+    const int fd = open(to.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
+    if (fd < 0) {
+        const int e = errno;
+        ngsq_bam_close(bam);
+        bail(std::string("creating SAM output file: ") + strerror(e) + " (os error " + std::to_string(e) + ")");
+    }
+    const uint32_t n_refs = ngsq_bam_n_refs(bam);
+    std::vector<uint32_t> lens(n_refs);
+    for (uint32_t r = 0; r < n_refs; r++) lens[r] = ngsq_bam_ref_len(bam, r);
+    ngsq_config cfg{};
+    cfg.struct_size = sizeof cfg;
+    cfg.facets = 0;
+    cfg.device = device;
+    cfg.n_refs = n_refs;
+    cfg.ref_len = lens.data();
+    ngsq_ctx *ctx = nullptr;
+    if (ngsq_create(&cfg, &ctx) != NGSQ_OK) {
+        close(fd);
+        bail(ngsq_last_global_error());
+    }
+    // RecordCounter::time_to_break (utils/display.rs:58-63) is tested behind the write: -n N writes max(N, 1) records
+    const uint64_t max_records = has_n ? std::max<unsigned long long>(n, 1) : 0;
+    ngsq_sam_report rep{};
+    const int rc = ngsq_bam_write_sam(bam, ctx, fd, max_records, 0, &rep);
+    const std::string msg = rc ? ngsq_bam_last_error() : "";
+    const int close_rc = close(fd), close_errno = errno;
+    ngsq_destroy(ctx);
+    ngsq_bam_close(bam);
+    if (rc) bail(msg);
+    if (close_rc) bail(std::string("writing SAM record: ") + strerror(close_errno) + " (os error " + std::to_string(close_errno) + ")");
+    // RecordCounter::inc (display.rs:43-52): one line per million records written
+    for (uint64_t m = 1; m <= rep.records / 1000000; m++) logf(2, "  [*] Processed %s records.", with_commas(m * 1000000).c_str());
+    if (g_level >= 3)
+        fprintf(stderr, "[ngs] convert: %llu records in %llu batches, %llu header + %llu text bytes; ingest %.1f ms, format %.1f ms, copy %.1f ms, "
+                        "write %.1f ms, total %.1f ms\n",
+                (unsigned long long)rep.records, (unsigned long long)rep.batches, (unsigned long long)rep.header_bytes,
+                (unsigned long long)rep.text_bytes, rep.scan_ms, rep.format_ms, rep.copy_ms, rep.write_ms, rep.total_ms);
+    return 0;
+}
+
 #define CHECK(ctx, expr)                                                                                   \
     do {                                                                                                   \
         const int rc_ = (expr);                                                                            \
@@ -373,13 +490,14 @@ static void milestone(const char *what) {
 
 int main(int argc, char **argv) {
     milestone("main");
-    { // `ngs [-q|-v] index ...`: its own arguments (the qc parser below never sees them)
+    { // `ngs [-q|-v] index ...` and `ngs [-q|-v] convert ...`: their own arguments (the qc parser below never sees them)
         int k = 1;
         while (k < argc && (!strcmp(argv[k], "-q") || !strcmp(argv[k], "--quiet") || !strcmp(argv[k], "-v") || !strcmp(argv[k], "--verbose"))) {
             g_level = argv[k][1] == 'q' || !strcmp(argv[k], "--quiet") ? 0 : 3;
             k++;
         }
         if (k < argc && !strcmp(argv[k], "index")) return index_main(argc, argv, k);
+        if (k < argc && !strcmp(argv[k], "convert")) return convert_main(argc, argv, k);
     }
     Args a;
     std::vector<std::string> pos;

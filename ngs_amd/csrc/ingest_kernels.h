@@ -7,6 +7,8 @@
 
 #include "kernels.h" // NGSQ_FOREGROUND_WAVE
 
+struct ngsq_bam;
+
 // Every vector-memory operation this wave has issued (loads, stores, atomics without a result) has been acknowledged by the L2
 // when this returns: orders device-scope atomics in front of a later one without a release fence (k_rec_fixed's ticket).
 #define NGSQ_WAIT_VMEM() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
@@ -21,6 +23,19 @@ struct BgzfBlock {
     uint32_t isize;   // ISIZE: decompressed bytes (<= 65536)
     uint32_t crc;     // CRC32 of the decompressed bytes
     uint32_t pad;
+};
+
+// Where the records of the batch the device ingest handed out last came from: the records' own bytes and the blocks that
+// held them.  Read by `ngs index` (a record's chunk positions: the position behind its last byte, htslib's rule, DESIGN.md
+// section 12.1) and by `ngs convert` (the fields the SAM text copies: DESIGN.md section 13).
+struct BatchOrigin {
+    const uint8_t *raw;      // the ingest's view of the inflated stream
+    const uint64_t *rec_off; // [n] view offset of every record of the batch (its block_size field)
+    const BgzfBlock *blocks; // the chunk's block table, out_off relative to the chunk's first byte (view offset - carry)
+    const uint64_t *coff;    // [n_blocks] file offset of every block
+    uint32_t n_blocks;
+    uint64_t carry;          // view bytes in front of the chunk's first byte
+    uint64_t next_coff;      // file offset behind the chunk's last block
 };
 
 // per-block result codes written by the inflate kernel
@@ -137,5 +152,8 @@ hipError_t launch_exclusive_scan_u64(uint64_t *data, uint64_t n_plus_1, void *tm
 // c.flag .. c.l_seq filled by launch_rec_fixed, var_base from it
 hipError_t launch_rec_var(const uint8_t *raw, const uint64_t *var_base, uint64_t n, const RecColumns &c, uint64_t seq_bytes,
                           uint64_t qual_bytes, hipStream_t s);
+
+// bam_device_reader.cpp: the origin of the last batch of ngsq_bam_next_batch_device (valid until the next call)
+int bam_device_batch_origin(ngsq_bam *b, BatchOrigin *out);
 
 } // namespace ngsq

@@ -229,6 +229,13 @@ class IndexReport(C.Structure):
                 ("scan_ms", C.c_double), ("write_ms", C.c_double)]
 
 
+# ---- include/ngsq_sam.h -----------------------------------------------------------------------
+class SamReport(C.Structure):
+    _fields_ = [("records", C.c_uint64), ("header_bytes", C.c_uint64), ("text_bytes", C.c_uint64), ("batches", C.c_uint64),
+                ("scan_ms", C.c_double), ("format_ms", C.c_double), ("copy_ms", C.c_double), ("write_ms", C.c_double),
+                ("total_ms", C.c_double)]
+
+
 # ---- include/ngsq_comm.h ----------------------------------------------------------------------
 COMM_ID_BYTES = 128
 COMM_MAX_WORLD = 64
@@ -373,6 +380,8 @@ PROTOTYPES = {
     "ngsq_bam_shard_end": (C.c_int, [C.c_void_p, C.POINTER(ShardInfo)]),
     # include/ngsq_index.h
     "ngsq_bam_build_index": (C.c_int, [C.c_void_p, ctx_p, C.c_char_p, C.POINTER(IndexReport)]),
+    # include/ngsq_sam.h
+    "ngsq_bam_write_sam": (C.c_int, [C.c_void_p, ctx_p, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(SamReport)]),
     "ngsq_bgzf_inflate_device": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p, C.c_int]),
     # include/ngsq_comm.h
     "ngsq_comm_last_error": (C.c_char_p, [comm_p]),

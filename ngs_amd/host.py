@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import json
+import os
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence
 
@@ -526,6 +527,41 @@ def build_bam_index(path: str, device: int = 0, bai_path: Optional[str] = None, 
             if rc != ffi.OK:
                 raise NgsqError(rc, (lib.ngsq_bam_last_error() or b"").decode("utf-8", "replace"))
             return {k: getattr(rep, k) for k, _ in ffi.IndexReport._fields_}
+        finally:
+            lib.ngsq_destroy(ctx)
+    finally:
+        lib.ngsq_bam_close(bam)
+
+
+def bam_to_sam(path: str, out_path: str, device: int = 0, max_records: int = 0, batch_records: int = 0, lib=None) -> Dict[str, float]:
+    """`ngs convert <BAM> <SAM>` in process (include/ngsq_sam.h): the SAM text of `path` written to out_path (created or
+    truncated), formatted on GPU `device` from the device ingest.  max_records: at most this many records (0: all; the
+    command line maps `-n N` to max(N, 1)); batch_records: records per ingest batch (0: the library's default).  Returns the
+    report; NgsqError on an open failure or a record without SAM text."""
+    lib = lib or ffi.load_library()
+    bam = C.c_void_p()
+    rc = lib.ngsq_bam_open(path.encode(), 0, C.byref(bam))
+    if rc != ffi.OK:
+        raise NgsqError(rc, "opening BAM input file: " + (lib.ngsq_bam_last_error() or b"").decode("utf-8", "replace"))
+    try:
+        n_refs = lib.ngsq_bam_n_refs(bam)
+        lens = np.array([lib.ngsq_bam_ref_len(bam, r) for r in range(n_refs)], dtype=np.uint32)
+        cfg = ffi.Config()
+        cfg.struct_size = C.sizeof(ffi.Config)
+        cfg.facets, cfg.device, cfg.n_refs = 0, device, n_refs
+        cfg.ref_len = lens.ctypes.data_as(ffi.u32p)
+        ctx = ffi.ctx_p()
+        _check(lib.ngsq_create(C.byref(cfg), C.byref(ctx)), None, lib)
+        try:
+            fd = os.open(out_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o666)
+            try:
+                rep = ffi.SamReport()
+                rc = lib.ngsq_bam_write_sam(bam, ctx, fd, max_records, batch_records, C.byref(rep))
+                if rc != ffi.OK:
+                    raise NgsqError(rc, (lib.ngsq_bam_last_error() or b"").decode("utf-8", "replace"))
+                return {k: getattr(rep, k) for k, _ in ffi.SamReport._fields_}
+            finally:
+                os.close(fd)
         finally:
             lib.ngsq_destroy(ctx)
     finally:
