@@ -50,6 +50,8 @@ uint32_t ngsq_bam_n_refs(const ngsq_bam *bam);
 const char *ngsq_bam_ref_name(const ngsq_bam *bam, uint32_t i);
 uint32_t ngsq_bam_ref_len(const ngsq_bam *bam, uint32_t i);
 const char *ngsq_bam_header_text(const ngsq_bam *bam, uint64_t *len);
+/* 1 when the header's @HD line holds the field SO:coordinate (the whole field: SO:coordinateX does not count), else 0. */
+int ngsq_bam_sorted_by_coordinate(const ngsq_bam *bam);
 
 /* Decode up to max_records further records into `out` (host SoA columns owned
  * by the reader, valid until the next call / close).  out->n_records == 0 at end

@@ -16,7 +16,7 @@ SOURCES = ["kernels.hip", "qual_kernel.hip", "fields_kernel.hip", "cov_scan.hip"
            "bam_device.hip", "features_kernel.hip", "edits_kernel.hip", "exchange_kernels.hip", "comm.cpp", "exchange.cpp", "mem_pool.cpp", "context.cpp", "stager.cpp", "results.cpp", "bam_reader.cpp", "bam_device_reader.cpp", "synth_bam.cpp",
            "reference.cpp", "reference_kernels.hip", "bai_kernel.hip", "bai.cpp",
            "sam_kernel.hip", "sam.cpp"]
-HEADERS = ["kernels.h", "context.h", "comm.h", "mem_pool.h", "ingest_kernels.h", "bgzf.h", "reference_kernels.h", "../../include/ngsq.h",
+HEADERS = ["kernels.h", "context.h", "comm.h", "mem_pool.h", "bam_reader.h", "ingest_consumer.h", "ingest_kernels.h", "bgzf.h", "reference_kernels.h", "../../include/ngsq.h",
            "../../include/ngsq_reference.h", "../../include/ngsq_comm.h",
            "../../include/ngsq_shared.h", "../../include/ngsq_synth.h", "../../include/ngsq_bam.h", "../../include/ngsq_stage.h",
            "bai_kernels.h", "../../include/ngsq_index.h", "sam_kernels.h", "../../include/ngsq_sam.h"]
@@ -40,18 +40,20 @@ def up_to_date() -> bool:
     return all(os.path.getmtime(d) <= t for d in deps)
 
 
-CLI_SRC = os.path.join(CSRC, "cli", "ngs_main.cpp")
+CLI_DIR = os.path.join(CSRC, "cli")
+CLI_SOURCES = [os.path.join(CLI_DIR, f) for f in ("ngs_main.cpp", "qc.cpp", "index.cpp", "convert.cpp")]  # one file per command
+CLI_HEADERS = sorted(os.path.join(CLI_DIR, f) for f in os.listdir(CLI_DIR) if f.endswith(".h"))
+CLI_PUBLIC_HEADERS = [os.path.join(HERE, "..", "include", f) for f in (
+    "ngsq.h", "ngsq_bam.h", "ngsq_comm.h", "ngsq_index.h", "ngsq_reference.h", "ngsq_sam.h", "ngsq_stage.h")]
 CLI_OUT = os.path.join(HERE, "ngs")
 
 
 def build_cli(force: bool = False, verbose: bool = True) -> str:
-    """The `ngs qc` command line (host C++ only), linked against libngsq.so next to it."""
-    deps = [CLI_SRC, OUT, os.path.join(HERE, "..", "include", "ngsq.h"), os.path.join(HERE, "..", "include", "ngsq_bam.h"),
-            os.path.join(HERE, "..", "include", "ngsq_reference.h"), os.path.join(HERE, "..", "include", "ngsq_index.h"),
-            os.path.join(CSRC, "cli", "gff_loader.h")]
+    """The `ngs` command line (host C++ only), linked against libngsq.so next to it."""
+    deps = CLI_SOURCES + CLI_HEADERS + CLI_PUBLIC_HEADERS + [OUT]
     if not force and os.path.exists(CLI_OUT) and all(os.path.getmtime(d) <= os.path.getmtime(CLI_OUT) for d in deps):
         return CLI_OUT
-    cmd = ["g++", "-O2", "-std=c++17", "-Wall", CLI_SRC, "-L" + HERE, "-lngsq", "-Wl,-rpath,$ORIGIN",
+    cmd = ["g++", "-O2", "-std=c++17", "-Wall"] + CLI_SOURCES + ["-L" + HERE, "-lngsq", "-Wl,-rpath,$ORIGIN",
            "-Wl,-rpath-link," + "/opt/rocm/lib", "-lz", "-lpthread", "-o", CLI_OUT + ".tmp"]
     if verbose:
         print("[ngs_amd.build]", " ".join(cmd), flush=True)

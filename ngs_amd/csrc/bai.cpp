@@ -7,7 +7,6 @@
 #include <unistd.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -15,76 +14,13 @@
 
 #include "../../include/ngsq_index.h"
 #include "bai_kernels.h"
-#include "bam_reader.h"
 #include "bgzf.h"
 #include "context.h"
-#include "mem_pool.h"
+#include "ingest_consumer.h"
 
 using namespace ngsq;
 
 namespace {
-
-double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-// a device array from the process's block cache; grow() keeps the contents
-template <typename T> struct DevArr {
-    T *p = nullptr;
-    size_t cap = 0, bytes = 0;
-    hipError_t reserve(size_t n, hipStream_t s = nullptr, bool keep = false) {
-        if (n <= cap) return hipSuccess;
-        const size_t want = std::max(n + 64, cap * 2);
-        void *q = nullptr;
-        size_t got = 0;
-        hipError_t e = pool_device_alloc(&q, want * sizeof(T), &got);
-        if (e != hipSuccess) return e;
-        if (keep && p && cap) {
-            e = hipMemcpyAsync(q, p, cap * sizeof(T), hipMemcpyDeviceToDevice, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s); // (the old block goes back to the cache below)
-            if (e != hipSuccess) {
-                pool_device_free(q, got);
-                return e;
-            }
-        }
-        pool_device_free(p, bytes);
-        p = static_cast<T *>(q);
-        cap = got / sizeof(T);
-        bytes = got;
-        return hipSuccess;
-    }
-    ~DevArr() { pool_device_free(p, bytes); }
-};
-
-struct Pinned {
-    unsigned long long *h = nullptr, *dev = nullptr;
-    ~Pinned() {
-        if (h) (void)hipHostFree(h);
-    }
-};
-
-#define IHIP(expr)                                                                                           \
-    do {                                                                                                     \
-        hipError_t e_ = (expr);                                                                              \
-        if (e_ != hipSuccess) return ngsq_bam_fail(NGSQ_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-// @HD ... SO:coordinate (the reference: header.header().sort_order() == Coordinate)
-bool header_coordinate_sorted(const std::string &text) {
-    const size_t hd = text.rfind("@HD", 0) == 0 ? 0 : text.find("\n@HD");
-    if (hd == std::string::npos) return false;
-    const size_t beg = hd == 0 ? 0 : hd + 1, eol = text.find('\n', beg);
-    const std::string line = text.substr(beg, eol == std::string::npos ? std::string::npos : eol - beg);
-    size_t k = 0;
-    while (k <= line.size()) {
-        const size_t tab = line.find('\t', k);
-        const std::string field = line.substr(k, tab == std::string::npos ? std::string::npos : tab - k);
-        if (field == "SO:coordinate") return true;
-        if (tab == std::string::npos) break;
-        k = tab + 1;
-    }
-    return false;
-}
 
 // The virtual position behind the header's last byte: the first record's chunk start (the header is read on the host at
 // open; this walks the BGZF framing of its blocks only).  header_bytes = decompressed bytes in front of the first record.
@@ -148,13 +84,12 @@ constexpr uint32_t LIN_MAX = 1u << 15;    // 2^29 / 16384: the windows of the BA
 extern "C" int ngsq_bam_build_index(ngsq_bam *b, ngsq_ctx *c, const char *bai_path, ngsq_index_report *out) {
     if (!b || !c || !bai_path) return ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "null argument");
     if (out) memset(out, 0, sizeof *out);
-    if (b->dev || b->host_mode || b->n_read)
-        return ngsq_bam_fail(NGSQ_ERR_STATE, "%s: an index is built from a reader no record has been read from", b->path.c_str());
+    if (const int rc = require_fresh_reader(b, "an index is built")) return rc;
     struct stat sb;
     if (stat(bai_path, &sb) == 0)
         return ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT,
                              "refusing to overwrite existing index file: %s. Please delete and rerun if you'd like to replace it.", bai_path);
-    if (!header_coordinate_sorted(b->header_text))
+    if (!ngsq_bam_sorted_by_coordinate(b))
         return ngsq_bam_fail(NGSQ_ERR_UNSORTED, "the input BAM must be coordinate-sorted to be indexed");
     const double t0 = now_ms();
     uint64_t hdr_endv = 0;
@@ -162,7 +97,7 @@ extern "C" int ngsq_bam_build_index(ngsq_bam *b, ngsq_ctx *c, const char *bai_pa
         const int rc = header_end_voffset(b, b->header_bytes, &hdr_endv);
         if (rc) return rc;
     }
-    IHIP(hipSetDevice(c->device));
+    BHIP(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     const uint32_t n_refs = (uint32_t)b->ref_lens.size();
     // ---- device state: linear windows per sequence, unmapped counts, the carry, the run list
@@ -186,16 +121,16 @@ extern "C" int ngsq_bam_build_index(ngsq_bam *b, ngsq_ctx *c, const char *bai_pa
         memcpy(setup.data() + state_words, lin_base.data(), n_refs * sizeof(uint64_t));
         memcpy(setup.data() + state_words + n_refs, lin_cap.data(), n_refs * sizeof(uint32_t));
     }
-    DevArr<uint64_t> d_setup;
-    DevArr<unsigned long long> d_lin, d_unm;
-    DevArr<uint64_t> d_flag, d_scan;
-    DevArr<BaiRun> d_tmp, d_runs;
-    IHIP(d_setup.reserve(setup.size()));
-    IHIP(d_lin.reserve(n_win + 1));
-    IHIP(d_unm.reserve(n_refs + 1));
-    IHIP(hipMemcpyAsync(d_setup.p, setup.data(), setup.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    IHIP(hipMemsetAsync(d_lin.p, 0xFF, (n_win + 1) * sizeof(unsigned long long), st));
-    IHIP(hipMemsetAsync(d_unm.p, 0, (n_refs + 1) * sizeof(unsigned long long), st));
+    DevArray<uint64_t> d_setup, d_flag;
+    DevArray<unsigned long long> d_lin, d_unm;
+    DevArray<BaiRun> d_tmp, d_runs;
+    ScanScratch scan;
+    BHIP(d_setup.reserve(setup.size()));
+    BHIP(d_lin.reserve(n_win + 1));
+    BHIP(d_unm.reserve(n_refs + 1));
+    BHIP(hipMemcpyAsync(d_setup.p, setup.data(), setup.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    BHIP(hipMemsetAsync(d_lin.p, 0xFF, (n_win + 1) * sizeof(unsigned long long), st));
+    BHIP(hipMemsetAsync(d_unm.p, 0, (n_refs + 1) * sizeof(unsigned long long), st));
     BaiState *d_state = reinterpret_cast<BaiState *>(d_setup.p);
     BaiLinear L;
     L.lin = d_lin.p;
@@ -204,69 +139,63 @@ extern "C" int ngsq_bam_build_index(ngsq_bam *b, ngsq_ctx *c, const char *bai_pa
     L.unmapped = d_unm.p;
     L.n_refs = n_refs;
     // results the host reads: [count of runs | state words | unmapped | n_intv] in mapped pinned memory
-    Pinned pin;
+    MappedBuf pin;
     const size_t pin_words = 8 + BAI_HOST_STATE_WORDS + 2 * (size_t)n_refs;
-    {
-        void *h = nullptr, *dv = nullptr;
-        IHIP(hipHostMalloc(&h, pin_words * sizeof(unsigned long long), hipHostMallocMapped));
-        pin.h = static_cast<unsigned long long *>(h);
-        memset(pin.h, 0, pin_words * sizeof(unsigned long long));
-        IHIP(hipHostGetDevicePointer(&dv, h, 0));
-        pin.dev = static_cast<unsigned long long *>(dv);
-    }
-    unsigned long long *const host_count = pin.dev, *const host_fin = pin.dev + 8;
+    BHIP(pin.reserve(pin_words * sizeof(unsigned long long)));
+    memset(pin.h, 0, pin_words * sizeof(unsigned long long));
+    const unsigned long long *const pin_h = static_cast<const unsigned long long *>(pin.h);
+    unsigned long long *const host_count = static_cast<unsigned long long *>(pin.dev), *const host_fin = host_count + 8;
     hipEvent_t ev = nullptr;
-    IHIP(pool_event_get(&ev));
+    BHIP(pool_event_get(&ev));
     struct EvPut {
         hipEvent_t e;
         ~EvPut() { pool_event_put(e); }
     } ev_put{ev};
+    std::vector<BaiRun> R; // what the end copies to the host: the run list and the windows
+    std::vector<unsigned long long> lin;
+    // Every way out below waits for the stream first: a gather or a copy may still be queued on it when an error returns,
+    // and the arrays above go back to the block cache or the heap when they leave scope (declared behind them: it runs first).
+    struct StreamDrain {
+        hipStream_t s;
+        ~StreamDrain() { (void)hipStreamSynchronize(s); }
+    } drain{st};
     // ---- the scan: every batch of the device ingest, in file order
     uint64_t records = 0, runs = 0;
     uint32_t parity = 0;
     bool pending = false; // a gather has been queued whose count the host has not read yet
     for (;;) {
         ngsq_batch bt;
-        const int rc = ngsq_bam_next_batch_device(b, c, BATCH_RECORDS, &bt);
-        if (rc) return rc;
+        BatchOrigin o;
+        if (const int rc = next_batch_with_origin(b, c, BATCH_RECORDS, &bt, &o)) return rc;
         if (pending) { // (the ingest has waited for its own kernels, queued behind that gather: this returns at once)
-            IHIP(hipEventSynchronize(ev));
-            runs = pin.h[0];
+            BHIP(hipEventSynchronize(ev));
+            runs = pin_h[0];
             pending = false;
         }
         const uint64_t n = bt.n_records;
         if (!n) break;
-        BatchOrigin o;
-        {
-            const int rc2 = bam_device_batch_origin(b, &o);
-            if (rc2) return rc2;
-        }
-        IHIP(d_flag.reserve(n + 1));
-        IHIP(d_tmp.reserve(n));
-        IHIP(d_runs.reserve(runs + n, st, true));
-        size_t tmp_bytes = 0;
-        IHIP(launch_exclusive_scan_u64(d_flag.p, n + 1, nullptr, &tmp_bytes, st));
-        IHIP(d_scan.reserve(tmp_bytes / sizeof(uint64_t) + 1));
+        BHIP(d_flag.reserve(n + 1));
+        BHIP(d_tmp.reserve(n));
+        BHIP(d_runs.reserve_keep(runs + n, st));
         {
             KernelTimer kt(c, K_REC_INDEX, n * 16);
-            IHIP(launch_bai_records(bt, o, d_state, parity, L, d_flag.p, d_tmp.p, st));
-            tmp_bytes = d_scan.cap * sizeof(uint64_t);
-            IHIP(launch_exclusive_scan_u64(d_flag.p, n + 1, d_scan.p, &tmp_bytes, st));
-            IHIP(launch_bai_gather(d_flag.p, d_tmp.p, n, d_runs.p, runs, host_count, st));
+            BHIP(launch_bai_records(bt, o, d_state, parity, L, d_flag.p, d_tmp.p, st));
+            BHIP(scan.exclusive_scan(d_flag.p, n + 1, st));
+            BHIP(launch_bai_gather(d_flag.p, d_tmp.p, n, d_runs.p, runs, host_count, st));
         }
-        IHIP(hipEventRecord(ev, st));
+        BHIP(hipEventRecord(ev, st));
         pending = true;
         parity ^= 1u;
         records += n;
     }
     // ---- the end: linear gaps filled on the device, then the run list and the windows to the host
-    IHIP(launch_bai_finish(L, d_state, parity, host_fin, st));
-    std::vector<BaiRun> R(runs);
-    std::vector<unsigned long long> lin(n_win);
-    if (runs) IHIP(hipMemcpyAsync(R.data(), d_runs.p, runs * sizeof(BaiRun), hipMemcpyDeviceToHost, st));
-    if (n_win) IHIP(hipMemcpyAsync(lin.data(), d_lin.p, n_win * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    IHIP(hipStreamSynchronize(st));
-    const unsigned long long *fin = pin.h + 8;
+    BHIP(launch_bai_finish(L, d_state, parity, host_fin, st));
+    R.resize(runs);
+    lin.resize(n_win);
+    if (runs) BHIP(hipMemcpyAsync(R.data(), d_runs.p, runs * sizeof(BaiRun), hipMemcpyDeviceToHost, st));
+    if (n_win) BHIP(hipMemcpyAsync(lin.data(), d_lin.p, n_win * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    BHIP(hipStreamSynchronize(st));
+    const unsigned long long *fin = pin_h + 8;
     if (fin[0] != ~0ull)
         return ngsq_bam_fail(NGSQ_ERR_UNSORTED, "%s: record %llu (0-based) is out of coordinate order: the input BAM must be coordinate-sorted to be indexed",
                              b->path.c_str(), fin[0]);

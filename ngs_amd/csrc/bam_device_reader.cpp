@@ -15,7 +15,6 @@
 #include <unistd.h>
 
 #include <algorithm>
-#include <chrono>
 #include <condition_variable>
 #include <mutex>
 #include <string>
@@ -23,12 +22,10 @@
 #include <vector>
 
 #include "../../include/ngsq_bam.h"
-#include "bam_reader.h"
 #include "bai_kernels.h"
 #include "bgzf.h"
 #include "context.h"
-#include "ingest_kernels.h"
-#include "mem_pool.h"
+#include "ingest_consumer.h"
 
 using namespace ngsq;
 
@@ -66,58 +63,10 @@ const char *inflate_status_text(uint32_t s) {
 }
 
 
-// growable device buffer
-// a device array that only grows; its memory comes from (and goes back to) the process's block cache (mem_pool.h)
-template <typename T> struct DevBuf {
-    T *p = nullptr;
-    size_t cap = 0;   // elements
-    size_t bytes = 0; // of the block behind p
-    hipError_t reserve(size_t n, bool keep = false) {
-        if (n <= cap) return hipSuccess;
-        const size_t want = n + n / 8 + 64;
-        void *q = nullptr;
-        size_t got = 0;
-        hipError_t e = ngsq::pool_device_alloc(&q, want * sizeof(T), &got);
-        if (e != hipSuccess) return e;
-        if (keep && p && cap) (void)hipMemcpy(q, p, cap * sizeof(T), hipMemcpyDeviceToDevice);
-        ngsq::pool_device_free(p, bytes);
-        p = static_cast<T *>(q);
-        cap = got / sizeof(T);
-        bytes = got;
-        return hipSuccess;
-    }
-    ~DevBuf() { ngsq::pool_device_free(p, bytes); }
-};
-
-// pinned host memory the device addresses directly (hipHostMalloc: mapped and coherent), grown on demand
-struct PinBuf {
-    void *h = nullptr, *dev = nullptr; // the same memory as the host and as the device see it
-    size_t cap = 0;
-    hipError_t reserve(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (h) (void)hipHostFree(h);
-        h = dev = nullptr;
-        cap = 0;
-        const size_t want = bytes + bytes / 4 + 4096;
-        hipError_t e = hipHostMalloc(&h, want, hipHostMallocMapped);
-        if (e != hipSuccess) return e;
-        e = hipHostGetDevicePointer(&dev, h, 0);
-        if (e != hipSuccess) return e;
-        cap = want;
-        return hipSuccess;
-    }
-    ~PinBuf() {
-        if (h) (void)hipHostFree(h);
-    }
-};
-
 // NGSQ_INGEST_TRACE=1: wall-clock of the ingest stages on stderr (measurement aid)
 bool trace_on() {
     static const bool on = getenv("NGSQ_INGEST_TRACE") && atoi(getenv("NGSQ_INGEST_TRACE"));
     return on;
-}
-double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
 // Keep the calling thread (and the threads it starts) on the CPUs of the NUMA node the device hangs off.  The reader
@@ -194,7 +143,7 @@ struct DeviceIngest {
         std::vector<uint64_t> coff; // file offset of every block of `blocks`
         bool ready = false, last = false; // last: the byte range ends with this chunk
         std::string err;
-        PinBuf tab; // [block table | file offsets], pinned: the reader thread sends them behind the chunk's bytes, on the copy stream
+        MappedBuf tab; // [block table | file offsets], pinned: the reader thread sends them behind the chunk's bytes, on the copy stream
     } hc[4];
     // Round 4: a chunk's context -- pinned buffer, device copy of the compressed bytes, block tables, Pending -- is one of NC
     // = 4 used in turn (chunk j: context j % 4), its inflated bytes go to one of NR = 3 raw buffers (j % 3), and the inflates
@@ -208,7 +157,7 @@ struct DeviceIngest {
     static constexpr uint64_t INFLATE_AHEAD = 2; // inflates queued beyond the chunk being parsed
     // the compressed bytes of a chunk cross PCIe on their own stream as soon as the reader thread has
     // framed them, i.e. while the GPU works on the previous chunk
-    DevBuf<uint8_t> d_comp_slot[NC];
+    DevArray<uint8_t> d_comp_slot[NC];
     hipStream_t copy_stream = nullptr;
     hipEvent_t h2d_done[NC] = {nullptr, nullptr, nullptr, nullptr};
     bool h2d_issued[NC] = {false, false, false, false};
@@ -233,7 +182,7 @@ struct DeviceIngest {
         // overlapped, rounds 1 and 2)
         // (the block table and the file offsets travel the other way through the same pinned block: a copy FROM pageable
         // memory is staged, and waits for the stream too when the staging buffers are in use)
-        PinBuf pin; // [status | block table | file offsets]
+        MappedBuf pin; // [status | block table | file offsets]
         uint32_t *status = nullptr;
         BgzfBlock *pin_blocks = nullptr;
         uint64_t *pin_coff = nullptr;
@@ -241,34 +190,35 @@ struct DeviceIngest {
         int rslot = 0; // the raw buffer its bytes are inflated to
         std::string err;
     } pend[NC];
-    PinBuf h_cand, h_seg, h_small; // the candidate table, the segments' verdicts, a few result words: host <-> device without DMA
+    MappedBuf h_cand, h_seg, h_small; // the candidate table, the segments' verdicts, a few result words: host <-> device without DMA
     // The block table and the blocks' file offsets of a chunk are read by its inflate AND, later, by the column kernels of its
     // batches (the records' ids): they belong to the chunk's context, which goes back to the reader thread when the chunk is
     // RETIRED -- the next chunk has been taken and everything that reads this one's buffers has been queued on the context's
     // stream; retired_ev[k] marks that point of the stream, the reader's copies into context k wait for it.
-    DevBuf<uint64_t> d_coff_s[NC], d_record_id;
-    DevBuf<BgzfBlock> d_blocks_s[NC];
-    DevBuf<uint32_t> d_status_s[NC];
+    DevArray<uint64_t> d_coff_s[NC], d_record_id;
+    DevArray<BgzfBlock> d_blocks_s[NC];
+    DevArray<uint32_t> d_status_s[NC];
     hipEvent_t retired_ev[NC] = {nullptr, nullptr, nullptr, nullptr}, inf_done[NC] = {nullptr, nullptr, nullptr, nullptr};
     bool retired_set[NC] = {false, false, false, false}; // (under mu)
     uint64_t chunks_issued = 0, chunks_loaded = 0; // inflates queued / chunks taken by load_chunk
-    DevBuf<uint8_t> d_rawb[NR];
+    DevArray<uint8_t> d_rawb[NR];
     hipStream_t inf_stream[2] = {nullptr, nullptr}; // the inflates alternate between them (low priority: start_ingest)
     hipEvent_t raw_free[NR] = {nullptr, nullptr, nullptr};
     bool raw_free_set[NR] = {false, false, false};
     uint8_t *raw = nullptr; // the inflated bytes being indexed / cut into batches: d_raw (sharded mode) or a view into a raw buffer
     // device
-    DevBuf<uint8_t> d_comp, d_seq, d_qual, d_scan_tmp;
-    DevBuf<BgzfBlock> d_blocks;
-    DevBuf<uint32_t> d_status, d_l_seq, d_cigar;
-    DevBuf<RecPieces> d_pieces;
-    DevBuf<uint64_t> d_var_base;              // per record of the batch: offset of its CIGAR in raw
-    DevBuf<uint64_t> d_rec_off, d_len; // d_len: seq | qual | cigar lengths -> offsets
-    DevBuf<unsigned long long> d_small;       // REC_WORK_WORDS words shared by k_rec_offsets / k_rec_fixed (ingest_kernels.h RecWork)
+    DevArray<uint8_t> d_comp, d_seq, d_qual;
+    ScanScratch scan;
+    DevArray<BgzfBlock> d_blocks;
+    DevArray<uint32_t> d_status, d_l_seq, d_cigar;
+    DevArray<RecPieces> d_pieces;
+    DevArray<uint64_t> d_var_base;              // per record of the batch: offset of its CIGAR in raw
+    DevArray<uint64_t> d_rec_off, d_len; // d_len: seq | qual | cigar lengths -> offsets
+    DevArray<unsigned long long> d_small;       // REC_WORK_WORDS words shared by k_rec_offsets / k_rec_fixed (ingest_kernels.h RecWork)
     uint32_t inf_ctr_base[2] = {0, 0};        // what the decoders' counters (d_small[W_INF0 / W_INF1]) hold before the next launch
-    DevBuf<uint16_t> d_flag, d_n_cigar;
-    DevBuf<uint8_t> d_mapq;
-    DevBuf<int32_t> d_ref_id, d_pos, d_mate, d_tlen;
+    DevArray<uint16_t> d_flag, d_n_cigar;
+    DevArray<uint8_t> d_mapq;
+    DevArray<int32_t> d_ref_id, d_pos, d_mate, d_tlen;
     uint64_t raw_len = 0, tail_off = 0;
     uint64_t n_rec = 0, cursor = 0; // records indexed in the current chunk / handed out
     uint64_t blocks_done = 0;
@@ -340,12 +290,6 @@ constexpr uint64_t SHARD_EXTRA = CARRY_MAX + ((uint64_t)1 << 20);
 namespace {
 
 void free_ingest(DeviceIngest *d) { delete d; }
-
-#define BHIP(expr)                                                                                          \
-    do {                                                                                                    \
-        hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess) return ngsq_bam_fail(NGSQ_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 // The reader's pread workers: started once (they inherit the reader thread's CPU affinity), woken per request.
 // (Threads created anew for every 64 MiB step spent a quarter of the step getting onto CPUs of their own.)  A request is a
@@ -1460,17 +1404,13 @@ int ngsq_bam_next_batch_device(ngsq_bam *b, ngsq_ctx *c, uint64_t max_records, n
     const bool cig1 = max_ops <= 1;
     uint64_t so = (uint64_t)pitch_s * n, qo = (uint64_t)pitch_q * n, co = n;
     if (!fixed || !cig1) {
-        size_t tmp_bytes = 0;
-        BHIP(launch_exclusive_scan_u64(sl, n + 1, nullptr, &tmp_bytes, st));
-        BHIP(d->d_scan_tmp.reserve(tmp_bytes + 256));
         if (!fixed) {
             // SEQ and QUAL lengths (absent qualities take no bytes: the kernel looks) -> offsets; their totals come back
             BHIP(hipMemsetAsync(sl, 0, 2 * (n + 1) * sizeof(uint64_t), st));
             BHIP(launch_rec_lengths(d->raw, rec, n, sl, ql, nullptr, st));
             for (int k = 0; k < 2; k++) {
                 uint64_t *arr = d->d_len.p + (size_t)k * (n + 1);
-                size_t tb = d->d_scan_tmp.cap;
-                BHIP(launch_exclusive_scan_u64(arr, n + 1, d->d_scan_tmp.p, &tb, st));
+                BHIP(d->scan.exclusive_scan(arr, n + 1, st));
                 BHIP(launch_copy_words(static_cast<uint64_t *>(d->h_small.dev) + 24 + k, arr + n, sizeof(uint64_t), st));
             }
             BHIP(hipStreamSynchronize(st));
@@ -1480,8 +1420,7 @@ int ngsq_bam_next_batch_device(ngsq_bam *b, ngsq_ctx *c, uint64_t max_records, n
             col.qual_off = ql;
         }
         if (!cig1) { // the operations per record are there (k_rec_fixed), their sum too: the offsets need no wait
-            size_t tb = d->d_scan_tmp.cap;
-            BHIP(launch_exclusive_scan_u64(cl, n + 1, d->d_scan_tmp.p, &tb, st));
+            BHIP(d->scan.exclusive_scan(cl, n + 1, st));
             co = host_stats[H_SUMOPS];
             col.cigar_off = cl;
         }

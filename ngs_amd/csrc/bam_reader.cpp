@@ -262,6 +262,16 @@ const char *ngsq_bam_header_text(const ngsq_bam *b, uint64_t *len) {
     if (len) *len = b->header_text.size();
     return b->header_text.c_str();
 }
+// @HD ... SO:coordinate as a whole field of the line (the reference: header.header().sort_order() == Coordinate)
+int ngsq_bam_sorted_by_coordinate(const ngsq_bam *b) {
+    if (!b) return 0;
+    const std::string &text = b->header_text;
+    const size_t hd = text.rfind("@HD", 0) == 0 ? 0 : text.find("\n@HD");
+    if (hd == std::string::npos) return 0;
+    const size_t beg = hd == 0 ? 0 : hd + 1, eol = text.find('\n', beg);
+    const std::string line = "\t" + text.substr(beg, eol == std::string::npos ? std::string::npos : eol - beg) + "\t";
+    return line.find("\tSO:coordinate\t") != std::string::npos;
+}
 uint64_t ngsq_bam_records_read(const ngsq_bam *b) { return b ? b->n_read : 0; }
 
 int ngsq_bam_next_batch(ngsq_bam *b, uint64_t max_records, ngsq_batch *out) {

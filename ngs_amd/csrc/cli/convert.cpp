@@ -1,0 +1,122 @@
+// convert.cpp -- `ngs convert` (src/convert/command.rs:26-172, src/convert/bam.rs:24-70): BAM to SAM, the
+// text formatted on the GPU by ngsq_bam_write_sam (include/ngsq_sam.h).  BAM to SAM only in this build.
+#include <fcntl.h>
+
+#include <algorithm>
+#include <cerrno>
+
+#include "../../../include/ngsq_sam.h"
+#include "cli.h"
+
+namespace {
+
+struct ConvertArgs {
+    std::vector<std::string> pos;
+    bool has_n = false, has_fasta = false; // (-r and -c take no part in BAM to SAM, as in the reference)
+    unsigned long long n = 0;
+    int device = 0;
+};
+
+// false: --help has been answered
+bool parse_args(int argc, char **argv, int at, ConvertArgs *a) {
+    for (int i = at + 1; i < argc; i++) {
+        const std::string s = argv[i];
+        auto val = [&](const char *name) { return option_value(argc, argv, &i, name); };
+        if (verbosity_option(argv[i])) continue;
+        if (s == "-h" || s == "--help") {
+            fprintf(stderr,
+                    "Usage: ngs convert [OPTIONS] <FROM> <TO>\n\n"
+                    "Arguments:\n"
+                    "  <FROM>  Path to the source file from which we are converting\n"
+                    "  <TO>    Path to the destination file to which we are converting\n\n"
+                    "Options:\n"
+                    "  -n, --num-records <USIZE>\n"
+                    "          Number of records to process before exiting the conversion\n"
+                    "  -r, --reference-fasta <REFERENCE_FASTA>\n"
+                    "          If available, the FASTA reference file used to generate the file\n"
+                    "  -c, --compression-strategy <COMPRESSION_STRATEGY>\n"
+                    "          [default: balanced] [possible values: best, balanced, fastest]\n"
+                    "      --device <N>\n"
+                    "          GPU the SAM text is formatted on (additive, this build) [default: 0]\n\n"
+                    "This build converts BAM to SAM only.\n");
+            return false;
+        } else if (s == "-n" || s == "--num-records") {
+            const std::string v = val("--num-records <USIZE>");
+            char *e = nullptr;
+            errno = 0;
+            a->n = strtoull(v.c_str(), &e, 10);
+            if (v.empty() || *e || errno || v[0] == '-' || v[0] == '+')
+                bail("invalid value '" + v + "' for '--num-records <USIZE>': invalid digit found in string");
+            a->has_n = true;
+        } else if (s == "-r" || s == "--reference-fasta") {
+            (void)val("--reference-fasta <REFERENCE_FASTA>");
+            a->has_fasta = true;
+        } else if (s == "-c" || s == "--compression-strategy") {
+            const std::string v = val("--compression-strategy <COMPRESSION_STRATEGY>");
+            if (v != "best" && v != "balanced" && v != "fastest")
+                bail("invalid value '" + v + "' for '--compression-strategy <COMPRESSION_STRATEGY>' [possible values: best, balanced, fastest]");
+        } else if (s == "--device") {
+            a->device = atoi(val("--device <N>").c_str());
+        } else if (!s.empty() && s[0] == '-' && s != "-") bail("unexpected argument '" + s + "' found");
+        else a->pos.push_back(s);
+    }
+    return true;
+}
+
+} // namespace
+
+// argv[at] is "convert".  Exit 0 on success, 1 on every error (anyhow::bail! in the reference).
+int convert_main(int argc, char **argv, int at) {
+    ConvertArgs a;
+    if (!parse_args(argc, argv, at, &a)) return 0;
+    const std::vector<std::string> &pos = a.pos;
+    if (pos.size() < 2) bail(pos.empty() ? "the following required arguments were not provided: <FROM> <TO>"
+                                         : "the following required arguments were not provided: <TO>");
+    if (pos.size() > 2) bail("unexpected argument '" + pos[2] + "' found");
+    const std::string &from = pos[0], &to = pos[1];
+    // BioinformaticsFileFormat::try_detect of <FROM>, then of <TO> (command.rs:63-82), with their contexts
+    const std::string ff = detect_format(from);
+    if (ff.empty()) bail("failed to detect from input filetype: " + from + ": Failed parsing of bioinformatics file format.");
+    const std::string tf = detect_format(to);
+    if (tf.empty()) bail("failed to deteect to input filetype: " + to + ": Failed parsing of bioinformatics file format.");
+    // the pairs the reference converts (command.rs:104-171)
+    const bool cram = (ff == "SAM" && tf == "CRAM") || (ff == "CRAM" && tf == "SAM") || (ff == "BAM" && tf == "CRAM") ||
+                      (ff == "CRAM" && tf == "BAM");
+    const bool reference_only = (ff == "SAM" && tf == "BAM") || (ff == "GFF" && tf == "Block-gzipped GFF") || cram;
+    if (cram && !a.has_fasta) bail("--reference-fasta is a required argument when converting to/from a CRAM file");
+    if (reference_only)
+        bail("Conversion from " + ff + " to " + tf + " is done by the reference `ngs convert` but not by this build, which converts BAM to SAM only");
+    if (!(ff == "BAM" && tf == "SAM")) bail("Conversion from " + ff + " to " + tf + " is not currently supported");
+    // to_sam_async: (1) open the BAM (IndexCheck::None), (2) create the SAM file, (3) the header, (4) every record
+    ngsq_bam *bam = nullptr;
+    if (ngsq_bam_open(from.c_str(), 0, &bam) != NGSQ_OK) bail(std::string("opening BAM input file: ") + ngsq_bam_last_error());
+    const int fd = open(to.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
+    if (fd < 0) {
+        const int e = errno;
+        ngsq_bam_close(bam);
+        bail(std::string("creating SAM output file: ") + strerror(e) + " (os error " + std::to_string(e) + ")");
+    }
+    ngsq_ctx *ctx = plain_context(bam, a.device);
+    if (!ctx) {
+        close(fd);
+        bail(ngsq_last_global_error());
+    }
+    // RecordCounter::time_to_break (utils/display.rs:58-63) is tested behind the write: -n N writes max(N, 1) records
+    const uint64_t max_records = a.has_n ? std::max<unsigned long long>(a.n, 1) : 0;
+    ngsq_sam_report rep{};
+    const int rc = ngsq_bam_write_sam(bam, ctx, fd, max_records, 0, &rep);
+    const std::string msg = rc ? ngsq_bam_last_error() : "";
+    const int close_rc = close(fd), close_errno = errno;
+    ngsq_destroy(ctx);
+    ngsq_bam_close(bam);
+    if (rc) bail(msg);
+    if (close_rc) bail(std::string("writing SAM record: ") + strerror(close_errno) + " (os error " + std::to_string(close_errno) + ")");
+    // RecordCounter::inc (display.rs:43-52): one line per million records written
+    for (uint64_t m = 1; m <= rep.records / 1000000; m++) logf(2, "  [*] Processed %s records.", with_commas(m * 1000000).c_str());
+    if (g_level >= 3)
+        fprintf(stderr, "[ngs] convert: %llu records in %llu batches, %llu header + %llu text bytes; ingest %.1f ms, format %.1f ms, copy %.1f ms, "
+                        "write %.1f ms, total %.1f ms\n",
+                (unsigned long long)rep.records, (unsigned long long)rep.batches, (unsigned long long)rep.header_bytes,
+                (unsigned long long)rep.text_bytes, rep.scan_ms, rep.format_ms, rep.copy_ms, rep.write_ms, rep.total_ms);
+    return 0;
+}

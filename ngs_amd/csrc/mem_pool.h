@@ -8,6 +8,8 @@
 #include <hip/hip_runtime_api.h>
 #include <stddef.h>
 
+#include <algorithm>
+
 namespace ngsq {
 
 // *got = bytes of the block (>= bytes); the same value goes back to pool_*_free.  Device blocks belong to the
@@ -35,5 +37,67 @@ hipError_t pool_event_get(hipEvent_t *e); // hipEventDisableTiming
 void pool_event_put(hipEvent_t e);
 // give everything that is cached back to the driver; returns the bytes released
 size_t pool_trim();
+
+// A device array that only grows; its memory comes from (and goes back to) the block cache.  reserve() does not keep the
+// contents and asks for an eighth more than it needs (the rule that sizes the ingest's GiB-scale buffers); reserve_keep()
+// copies them on `s`, waits for the copy, and at least doubles: filling an array that way copies O(log n) times.
+template <typename T> struct DevArray {
+    T *p = nullptr;
+    size_t cap = 0;   // elements
+    size_t bytes = 0; // of the block behind p
+    DevArray() = default;
+    DevArray(const DevArray &) = delete;
+    DevArray &operator=(const DevArray &) = delete;
+    hipError_t reserve(size_t n) { return n <= cap ? hipSuccess : grow(n + n / 8 + 64, false, nullptr); }
+    hipError_t reserve_keep(size_t n, hipStream_t s) { return n <= cap ? hipSuccess : grow(std::max(n + 64, cap * 2), true, s); }
+    ~DevArray() { pool_device_free(p, bytes); }
+
+  private:
+    hipError_t grow(size_t want, bool keep, hipStream_t s) {
+        void *q = nullptr;
+        size_t got = 0;
+        hipError_t e = pool_device_alloc(&q, want * sizeof(T), &got);
+        if (e != hipSuccess) return e;
+        if (keep && p && cap) {
+            e = hipMemcpyAsync(q, p, cap * sizeof(T), hipMemcpyDeviceToDevice, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s); // (the old block goes back to the cache below)
+            if (e != hipSuccess) {
+                pool_device_free(q, got);
+                return e;
+            }
+        }
+        pool_device_free(p, bytes);
+        p = static_cast<T *>(q);
+        cap = got / sizeof(T);
+        bytes = got;
+        return hipSuccess;
+    }
+};
+
+// pinned host memory the device addresses directly (hipHostMalloc: mapped and coherent), grown on demand without keeping
+// its contents: h and dev are the same memory as the host and as the device see it
+struct MappedBuf {
+    void *h = nullptr, *dev = nullptr;
+    size_t cap = 0; // bytes
+    MappedBuf() = default;
+    MappedBuf(const MappedBuf &) = delete;
+    MappedBuf &operator=(const MappedBuf &) = delete;
+    hipError_t reserve(size_t bytes) {
+        if (bytes <= cap) return hipSuccess;
+        if (h) (void)hipHostFree(h);
+        h = dev = nullptr;
+        cap = 0;
+        const size_t want = bytes + bytes / 4 + 4096;
+        hipError_t e = hipHostMalloc(&h, want, hipHostMallocMapped);
+        if (e != hipSuccess) return e;
+        e = hipHostGetDevicePointer(&dev, h, 0);
+        if (e != hipSuccess) return e;
+        cap = want;
+        return hipSuccess;
+    }
+    ~MappedBuf() {
+        if (h) (void)hipHostFree(h);
+    }
+};
 
 } // namespace ngsq

@@ -8,7 +8,6 @@
 #include <unistd.h>
 
 #include <algorithm>
-#include <chrono>
 #include <condition_variable>
 #include <cstdio>
 #include <cstring>
@@ -19,44 +18,13 @@
 #include <vector>
 
 #include "../../include/ngsq_sam.h"
-#include "bam_reader.h"
 #include "context.h"
-#include "mem_pool.h"
+#include "ingest_consumer.h"
 #include "sam_kernels.h"
 
 using namespace ngsq;
 
 namespace {
-
-double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-// a device array from the process's block cache, grown without keeping its contents
-template <typename T> struct DevBuf {
-    T *p = nullptr;
-    size_t cap = 0, bytes = 0;
-    hipError_t reserve(size_t n) {
-        if (n <= cap) return hipSuccess;
-        const size_t want = std::max(n + 64, cap + cap / 2);
-        void *q = nullptr;
-        size_t got = 0;
-        const hipError_t e = pool_device_alloc(&q, want * sizeof(T), &got);
-        if (e != hipSuccess) return e;
-        pool_device_free(p, bytes);
-        p = static_cast<T *>(q);
-        cap = got / sizeof(T);
-        bytes = got;
-        return hipSuccess;
-    }
-    ~DevBuf() { pool_device_free(p, bytes); }
-};
-
-#define SHIP(expr)                                                                                           \
-    do {                                                                                                     \
-        hipError_t e_ = (expr);                                                                              \
-        if (e_ != hipSuccess) return ngsq_bam_fail(NGSQ_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 constexpr uint64_t BATCH_RECORDS = (uint64_t)1 << 20;
 constexpr uint32_t RING_SLOTS = 4;
@@ -236,166 +204,161 @@ struct Events {
     }
 };
 
+// What the batches of one ngsq_bam_write_sam share.
+struct SamRun {
+    ngsq_bam *b;
+    ngsq_ctx *c;
+    hipStream_t st = nullptr;
+    uint64_t max_records, batch_records;
+    // the @SQ names on the device, the error word, the words the host reads
+    DevArray<uint64_t> d_setup;
+    unsigned long long *d_bad = nullptr;
+    SamRefs refs;
+    MappedBuf hw;
+    // the writer: a copy stream, the pinned ring, its thread
+    Writer w;
+    Events ev; // ready[2]; format brackets: size a/b, write a/b
+    DevArray<uint64_t> d_off, d_flist;
+    DevArray<uint8_t> d_fmark;
+    ScanScratch scan;
+    DevArray<char> d_text[2];
+    uint64_t records = 0, text_bytes = 0, batches = 0;
+    double scan_ms = 0, format_ms = 0;
+    bool write_pending = false; // the last write pass's bracket has not been added to format_ms yet
+
+    void add_write_time() {
+        float ms = 0;
+        if (write_pending && hipEventElapsedTime(&ms, ev.e[4], ev.e[5]) == hipSuccess) format_ms += ms;
+        write_pending = false;
+    }
+    int next_batch(bool *more);
+};
+
+// One batch of the device ingest, in file order: sized, scanned, written into a device buffer and handed to the writer.
+// *more = false: that was the last one (the file's end, max_records, or a writer that has failed: its error is read at the end).
+int SamRun::next_batch(bool *more) {
+    *more = false;
+    const uint64_t left = max_records ? max_records - records : ~0ull;
+    if (!left) return NGSQ_OK;
+    ngsq_batch bt;
+    BatchOrigin o;
+    const double s0 = now_ms();
+    const int rc = next_batch_with_origin(b, c, std::min(batch_records, left), &bt, &o);
+    scan_ms += now_ms() - s0;
+    if (rc) return rc;
+    const uint64_t n = bt.n_records;
+    if (!n) return NGSQ_OK;
+    BHIP(d_off.reserve(n + 1));
+    BHIP(d_fmark.reserve(n));
+    BHIP(d_flist.reserve(n + 1));
+    const SamFloats fl{d_fmark.p, d_flist.p + 1, reinterpret_cast<unsigned long long *>(d_flist.p)};
+    // sizes, offsets, and the batch's text bytes and error word to the host
+    BHIP(hipEventRecord(ev.e[2], st));
+    BHIP(launch_sam_size(bt, o, refs, d_off.p, d_bad, fl, st));
+    BHIP(scan.exclusive_scan(d_off.p, n + 1, st));
+    BHIP(launch_sam_total(d_off.p, n, d_bad, static_cast<unsigned long long *>(hw.dev), st));
+    BHIP(hipEventRecord(ev.e[3], st));
+    BHIP(hipEventSynchronize(ev.e[3]));
+    {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ev.e[2], ev.e[3]) == hipSuccess) format_ms += ms;
+    }
+    add_write_time();
+    const unsigned long long *const h = static_cast<const unsigned long long *>(hw.h);
+    const uint64_t bytes = h[0], bad = h[1];
+    if (bad != ~0ull)
+        return ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "writing SAM record: record %llu: %s", (unsigned long long)(bad >> SAM_ERR_BITS),
+                             sam_error_text((uint32_t)(bad & ((1u << SAM_ERR_BITS) - 1))));
+    // the buffer of batch k - 2 is this batch's once its copies have completed
+    const uint32_t slot = (uint32_t)(batches & 1);
+    if (batches >= 2 && !w.wait_copied(batches - 1)) return NGSQ_OK;
+    BHIP(d_text[slot].reserve(bytes + 1));
+    BHIP(hipEventRecord(ev.e[4], st));
+    BHIP(launch_sam_write(bt, o, refs, d_off.p, d_text[slot].p, fl, st));
+    BHIP(hipEventRecord(ev.e[5], st));
+    BHIP(hipEventRecord(ev.e[slot], st));
+    write_pending = true;
+    w.push(Job{d_text[slot].p, bytes, ev.e[slot], batches});
+    records += n;
+    text_bytes += bytes;
+    batches++;
+    *more = !w.werr;
+    return NGSQ_OK;
+}
+
 } // namespace
 
 extern "C" int ngsq_bam_write_sam(ngsq_bam *b, ngsq_ctx *c, int fd, uint64_t max_records, uint64_t batch_records, ngsq_sam_report *out) {
     if (!b || !c || fd < 0) return ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "null argument");
     if (out) memset(out, 0, sizeof *out);
-    if (b->dev || b->host_mode || b->n_read)
-        return ngsq_bam_fail(NGSQ_ERR_STATE, "%s: a SAM file is written from a reader no record has been read from", b->path.c_str());
+    if (const int rc = require_fresh_reader(b, "a SAM file is written")) return rc;
     const double t_begin = now_ms();
-    if (!batch_records) batch_records = BATCH_RECORDS;
     // ---- the header: the text the file holds, with a final newline
     std::string head = b->header_text;
     if (!head.empty() && head.back() != '\n') head += '\n';
     if (const int e = write_all(fd, head.data(), head.size()))
         return ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "writing SAM header: %s (os error %d)", strerror(e), e);
-    SHIP(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    // ---- the @SQ names on the device, the error word, the words the host reads
+    BHIP(hipSetDevice(c->device));
+    SamRun r;
+    r.b = b;
+    r.c = c;
+    r.st = c->stream;
+    r.max_records = max_records;
+    r.batch_records = batch_records ? batch_records : BATCH_RECORDS;
     const uint32_t n_refs = (uint32_t)b->ref_names.size();
     std::vector<uint64_t> setup(n_refs + 2, 0); // [bad | name_off[n_refs + 1]] then the names
     std::string names;
-    for (uint32_t r = 0; r < n_refs; r++) {
-        setup[1 + r] = names.size();
-        names += b->ref_names[r];
+    for (uint32_t k = 0; k < n_refs; k++) {
+        setup[1 + k] = names.size();
+        names += b->ref_names[k];
     }
     setup[1 + n_refs] = names.size();
     setup[0] = ~0ull;
-    DevBuf<uint64_t> d_setup;
-    SHIP(d_setup.reserve(setup.size() + (names.size() + 7) / 8));
-    SHIP(hipMemcpyAsync(d_setup.p, setup.data(), setup.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    if (!names.empty()) SHIP(hipMemcpyAsync(d_setup.p + setup.size(), names.data(), names.size(), hipMemcpyHostToDevice, st));
-    unsigned long long *const d_bad = reinterpret_cast<unsigned long long *>(d_setup.p);
-    SamRefs refs;
-    refs.names = reinterpret_cast<const char *>(d_setup.p + setup.size());
-    refs.name_off = d_setup.p + 1;
-    refs.n_refs = n_refs;
-    struct HostWords {
-        unsigned long long *h = nullptr;
-        ~HostWords() {
-            if (h) (void)hipHostFree(h);
-        }
-    } hw;
-    unsigned long long *h_dev = nullptr;
-    {
-        void *h = nullptr, *dv = nullptr;
-        SHIP(hipHostMalloc(&h, 8 * sizeof(unsigned long long), hipHostMallocMapped));
-        hw.h = static_cast<unsigned long long *>(h);
-        memset(hw.h, 0, 8 * sizeof(unsigned long long));
-        SHIP(hipHostGetDevicePointer(&dv, h, 0));
-        h_dev = static_cast<unsigned long long *>(dv);
-    }
-    // ---- the writer: a copy stream, the pinned ring, its thread
-    Writer w;
-    w.fd = fd;
-    w.device = c->device;
-    SHIP(pool_stream_get(false, &w.cs));
-    Events ev; // ready[2]; format brackets: size a/b, write a/b
-    SHIP(hipEventCreateWithFlags(&ev.e[0], hipEventDisableTiming));
-    SHIP(hipEventCreateWithFlags(&ev.e[1], hipEventDisableTiming));
-    for (int k = 2; k < 6; k++) SHIP(hipEventCreate(&ev.e[k]));
+    BHIP(r.d_setup.reserve(setup.size() + (names.size() + 7) / 8));
+    BHIP(hipMemcpyAsync(r.d_setup.p, setup.data(), setup.size() * sizeof(uint64_t), hipMemcpyHostToDevice, r.st));
+    if (!names.empty()) BHIP(hipMemcpyAsync(r.d_setup.p + setup.size(), names.data(), names.size(), hipMemcpyHostToDevice, r.st));
+    r.d_bad = reinterpret_cast<unsigned long long *>(r.d_setup.p);
+    r.refs.names = reinterpret_cast<const char *>(r.d_setup.p + setup.size());
+    r.refs.name_off = r.d_setup.p + 1;
+    r.refs.n_refs = n_refs;
+    BHIP(r.hw.reserve(8 * sizeof(unsigned long long)));
+    memset(r.hw.h, 0, 8 * sizeof(unsigned long long));
+    r.w.fd = fd;
+    r.w.device = c->device;
+    BHIP(pool_stream_get(false, &r.w.cs));
+    BHIP(hipEventCreateWithFlags(&r.ev.e[0], hipEventDisableTiming));
+    BHIP(hipEventCreateWithFlags(&r.ev.e[1], hipEventDisableTiming));
+    for (int k = 2; k < 6; k++) BHIP(hipEventCreate(&r.ev.e[k]));
+    Writer &w = r.w;
     w.th = std::thread([&w] { w.run(); });
-    DevBuf<uint64_t> d_off, d_scan, d_flist;
-    DevBuf<uint8_t> d_fmark;
     { // the per-record arrays for the largest batch asked for: a batch's write pass may still read them when the next one begins
-        const uint64_t n0 = std::min<uint64_t>(batch_records, max_records ? max_records : batch_records);
-        if (d_off.reserve(n0 + 1) != hipSuccess || d_fmark.reserve(n0) != hipSuccess || d_flist.reserve(n0 + 1) != hipSuccess)
+        const uint64_t n0 = std::min<uint64_t>(r.batch_records, max_records ? max_records : r.batch_records);
+        if (r.d_off.reserve(n0 + 1) != hipSuccess || r.d_fmark.reserve(n0) != hipSuccess || r.d_flist.reserve(n0 + 1) != hipSuccess)
             return ngsq_bam_fail(NGSQ_ERR_DEVICE, "allocating the SAM formatter's arrays for %llu records", (unsigned long long)n0);
     }
-    DevBuf<char> d_text[2];
     // ---- the scan: every batch of the device ingest, in file order
-    uint64_t records = 0, text_bytes = 0, batches = 0;
-    double scan_ms = 0, format_ms = 0;
-    bool write_pending = false; // the last write pass's bracket has not been added to format_ms yet
     int rc = NGSQ_OK;
-    auto add_write_time = [&]() {
-        float ms = 0;
-        if (write_pending && hipEventElapsedTime(&ms, ev.e[4], ev.e[5]) == hipSuccess) format_ms += ms;
-        write_pending = false;
-    };
-    for (;;) {
-        const uint64_t left = max_records ? max_records - records : ~0ull;
-        if (!left) break;
-        ngsq_batch bt;
-        const double s0 = now_ms();
-        rc = ngsq_bam_next_batch_device(b, c, std::min(batch_records, left), &bt);
-        scan_ms += now_ms() - s0;
-        if (rc) break;
-        const uint64_t n = bt.n_records;
-        if (!n) break;
-        BatchOrigin o;
-        if ((rc = bam_device_batch_origin(b, &o))) break;
-        size_t tmp_bytes = 0;
-#define SFAIL(expr)                                                                                  \
-    {                                                                                                \
-        hipError_t e_ = (expr);                                                                      \
-        if (e_ != hipSuccess) {                                                                      \
-            rc = ngsq_bam_fail(NGSQ_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_));             \
-            break;                                                                                   \
-        }                                                                                            \
-    }
-        SFAIL(d_off.reserve(n + 1));
-        SFAIL(d_fmark.reserve(n));
-        SFAIL(d_flist.reserve(n + 1));
-        const SamFloats fl{d_fmark.p, d_flist.p + 1, reinterpret_cast<unsigned long long *>(d_flist.p)};
-        SFAIL(launch_exclusive_scan_u64(d_off.p, n + 1, nullptr, &tmp_bytes, st));
-        SFAIL(d_scan.reserve(tmp_bytes / sizeof(uint64_t) + 1));
-        tmp_bytes = d_scan.cap * sizeof(uint64_t);
-        // sizes, offsets, and the batch's text bytes and error word to the host
-        SFAIL(hipEventRecord(ev.e[2], st));
-        SFAIL(launch_sam_size(bt, o, refs, d_off.p, d_bad, fl, st));
-        SFAIL(launch_exclusive_scan_u64(d_off.p, n + 1, d_scan.p, &tmp_bytes, st));
-        SFAIL(launch_sam_total(d_off.p, n, d_bad, h_dev, st));
-        SFAIL(hipEventRecord(ev.e[3], st));
-        SFAIL(hipEventSynchronize(ev.e[3]));
-        {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, ev.e[2], ev.e[3]) == hipSuccess) format_ms += ms;
-        }
-        add_write_time();
-        const uint64_t bytes = hw.h[0], bad = hw.h[1];
-        if (bad != ~0ull) {
-            rc = ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "writing SAM record: record %llu: %s", (unsigned long long)(bad >> SAM_ERR_BITS),
-                               sam_error_text((uint32_t)(bad & ((1u << SAM_ERR_BITS) - 1))));
-            break;
-        }
-        // the buffer of batch k - 2 is this batch's once its copies have completed
-        const uint32_t slot = (uint32_t)(batches & 1);
-        if (batches >= 2 && !w.wait_copied(batches - 1)) break;
-        SFAIL(d_text[slot].reserve(bytes + 1));
-        SFAIL(hipEventRecord(ev.e[4], st));
-        SFAIL(launch_sam_write(bt, o, refs, d_off.p, d_text[slot].p, fl, st));
-        SFAIL(hipEventRecord(ev.e[5], st));
-        SFAIL(hipEventRecord(ev.e[slot], st));
-        write_pending = true;
-        w.push(Job{d_text[slot].p, bytes, ev.e[slot], batches});
-        records += n;
-        text_bytes += bytes;
-        batches++;
-        if (w.werr) break;
-    }
-#undef SFAIL
+    for (bool more = true; more && rc == NGSQ_OK;) rc = r.next_batch(&more);
     if (rc == NGSQ_OK) {
-        const hipError_t e = hipStreamSynchronize(st);
+        const hipError_t e = hipStreamSynchronize(r.st);
         if (e != hipSuccess) rc = ngsq_bam_fail(NGSQ_ERR_DEVICE, "hipStreamSynchronize: %s", hipGetErrorString(e));
-        add_write_time();
+        r.add_write_time();
     }
     w.stop(); // (every queued copy is written, or skipped after a failed write)
     if (rc == NGSQ_OK && w.herr != hipSuccess)
         rc = ngsq_bam_fail(NGSQ_ERR_DEVICE, "copying the SAM text to the host: %s", hipGetErrorString(w.herr));
     if (rc == NGSQ_OK && w.werr) rc = ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "writing SAM record: %s (os error %d)", strerror(w.werr), w.werr);
     if (rc != NGSQ_OK) {
-        (void)hipStreamSynchronize(st); // (the device buffers go back to the cache: nothing may still use them)
+        (void)hipStreamSynchronize(r.st); // (the device buffers go back to the cache: nothing may still use them)
         return rc;
     }
     if (out) {
-        out->records = records;
+        out->records = r.records;
         out->header_bytes = head.size();
-        out->text_bytes = text_bytes;
-        out->batches = batches;
-        out->scan_ms = scan_ms;
-        out->format_ms = format_ms;
+        out->text_bytes = r.text_bytes;
+        out->batches = r.batches;
+        out->scan_ms = r.scan_ms;
+        out->format_ms = r.format_ms;
         out->copy_ms = w.copy_ms;
         out->write_ms = w.write_ms;
         out->total_ms = now_ms() - t_begin;

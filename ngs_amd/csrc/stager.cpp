@@ -1,7 +1,7 @@
 // stager.cpp -- include/ngsq_stage.h: one decoded record at a time into pinned structure-of-arrays columns, handed to
 // ngsq_process_batch when full.  The adapter under the reference's per-record trait calls (src/qc.rs:165,203-219;
 // src/qc/command.rs:305-316,356-397): INTEGRATION.md section 4 is written over these entry points, and the command line's
-// -n paths (cli/ngs_main.cpp) pick their records through it.
+// -n paths (cli/qc.cpp) pick their records through it.
 #include <hip/hip_runtime_api.h>
 
 #include <cstdarg>

@@ -372,6 +372,7 @@ PROTOTYPES = {
     "ngsq_bam_ref_name": (C.c_char_p, [C.c_void_p, C.c_uint32]),
     "ngsq_bam_ref_len": (C.c_uint32, [C.c_void_p, C.c_uint32]),
     "ngsq_bam_header_text": (C.c_char_p, [C.c_void_p, u64p]),
+    "ngsq_bam_sorted_by_coordinate": (C.c_int, [C.c_void_p]),
     "ngsq_bam_next_batch": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(Batch)]),
     "ngsq_bam_records_read": (C.c_uint64, [C.c_void_p]),
     "ngsq_bam_next_batch_device": (C.c_int, [C.c_void_p, ctx_p, C.c_uint64, C.POINTER(Batch)]),

@@ -6,6 +6,7 @@ Nothing here computes: every number comes out of libngsq.so.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import json
 import os
@@ -504,14 +505,14 @@ class QcContext:
         _check(self.lib.ngsq_state_upload(self._ctx, which, a.ctypes.data, a.nbytes), self._ctx, self.lib)
 
 
-def build_bam_index(path: str, device: int = 0, bai_path: Optional[str] = None, lib=None) -> Dict[str, float]:
-    """`ngs index` in process (include/ngsq_index.h): write the BAI of the coordinate-sorted BAM `path` to bai_path
-    (default "<path>.bai"), built on GPU `device` from the device ingest.  Returns the report; NgsqError on any refusal."""
-    lib = lib or ffi.load_library()
+@contextlib.contextmanager
+def _reader_and_plain_context(lib, path: str, device: int, open_context: str = ""):
+    """(reader, context) for the commands that walk a file through the device ingest without any QC facet: the BAM opened, a
+    context for its @SQ lengths on GPU `device`; both released on the way out.  open_context: prefix of the open failure."""
     bam = C.c_void_p()
     rc = lib.ngsq_bam_open(path.encode(), 0, C.byref(bam))
     if rc != ffi.OK:
-        raise NgsqError(rc, (lib.ngsq_bam_last_error() or b"").decode("utf-8", "replace"))
+        raise NgsqError(rc, open_context + (lib.ngsq_bam_last_error() or b"").decode("utf-8", "replace"))
     try:
         n_refs = lib.ngsq_bam_n_refs(bam)
         lens = np.array([lib.ngsq_bam_ref_len(bam, r) for r in range(n_refs)], dtype=np.uint32)
@@ -522,15 +523,26 @@ def build_bam_index(path: str, device: int = 0, bai_path: Optional[str] = None, 
         ctx = ffi.ctx_p()
         _check(lib.ngsq_create(C.byref(cfg), C.byref(ctx)), None, lib)
         try:
-            rep = ffi.IndexReport()
-            rc = lib.ngsq_bam_build_index(bam, ctx, (bai_path or path + ".bai").encode(), C.byref(rep))
-            if rc != ffi.OK:
-                raise NgsqError(rc, (lib.ngsq_bam_last_error() or b"").decode("utf-8", "replace"))
-            return {k: getattr(rep, k) for k, _ in ffi.IndexReport._fields_}
+            yield bam, ctx
         finally:
             lib.ngsq_destroy(ctx)
     finally:
         lib.ngsq_bam_close(bam)
+
+
+def _check_bam(rc: int, lib):
+    if rc != ffi.OK:
+        raise NgsqError(rc, (lib.ngsq_bam_last_error() or b"").decode("utf-8", "replace"))
+
+
+def build_bam_index(path: str, device: int = 0, bai_path: Optional[str] = None, lib=None) -> Dict[str, float]:
+    """`ngs index` in process (include/ngsq_index.h): write the BAI of the coordinate-sorted BAM `path` to bai_path
+    (default "<path>.bai"), built on GPU `device` from the device ingest.  Returns the report; NgsqError on any refusal."""
+    lib = lib or ffi.load_library()
+    with _reader_and_plain_context(lib, path, device) as (bam, ctx):
+        rep = ffi.IndexReport()
+        _check_bam(lib.ngsq_bam_build_index(bam, ctx, (bai_path or path + ".bai").encode(), C.byref(rep)), lib)
+        return {k: getattr(rep, k) for k, _ in ffi.IndexReport._fields_}
 
 
 def bam_to_sam(path: str, out_path: str, device: int = 0, max_records: int = 0, batch_records: int = 0, lib=None) -> Dict[str, float]:
@@ -539,30 +551,11 @@ def bam_to_sam(path: str, out_path: str, device: int = 0, max_records: int = 0, 
     command line maps `-n N` to max(N, 1)); batch_records: records per ingest batch (0: the library's default).  Returns the
     report; NgsqError on an open failure or a record without SAM text."""
     lib = lib or ffi.load_library()
-    bam = C.c_void_p()
-    rc = lib.ngsq_bam_open(path.encode(), 0, C.byref(bam))
-    if rc != ffi.OK:
-        raise NgsqError(rc, "opening BAM input file: " + (lib.ngsq_bam_last_error() or b"").decode("utf-8", "replace"))
-    try:
-        n_refs = lib.ngsq_bam_n_refs(bam)
-        lens = np.array([lib.ngsq_bam_ref_len(bam, r) for r in range(n_refs)], dtype=np.uint32)
-        cfg = ffi.Config()
-        cfg.struct_size = C.sizeof(ffi.Config)
-        cfg.facets, cfg.device, cfg.n_refs = 0, device, n_refs
-        cfg.ref_len = lens.ctypes.data_as(ffi.u32p)
-        ctx = ffi.ctx_p()
-        _check(lib.ngsq_create(C.byref(cfg), C.byref(ctx)), None, lib)
+    with _reader_and_plain_context(lib, path, device, "opening BAM input file: ") as (bam, ctx):
+        fd = os.open(out_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o666)
         try:
-            fd = os.open(out_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o666)
-            try:
-                rep = ffi.SamReport()
-                rc = lib.ngsq_bam_write_sam(bam, ctx, fd, max_records, batch_records, C.byref(rep))
-                if rc != ffi.OK:
-                    raise NgsqError(rc, (lib.ngsq_bam_last_error() or b"").decode("utf-8", "replace"))
-                return {k: getattr(rep, k) for k, _ in ffi.SamReport._fields_}
-            finally:
-                os.close(fd)
+            rep = ffi.SamReport()
+            _check_bam(lib.ngsq_bam_write_sam(bam, ctx, fd, max_records, batch_records, C.byref(rep)), lib)
+            return {k: getattr(rep, k) for k, _ in ffi.SamReport._fields_}
         finally:
-            lib.ngsq_destroy(ctx)
-    finally:
-        lib.ngsq_bam_close(bam)
+            os.close(fd)

@@ -1,4 +1,4 @@
-"""The `ngs qc` command line (ngs_amd/csrc/cli/ngs_main.cpp) against the reference's CLI contract
+"""The `ngs qc` command line (ngs_amd/csrc/cli/qc.cpp) against the reference's CLI contract
 (src/qc/command.rs:36-218, :226-421): flags, error texts, output file, and -- on a GPU -- the
 whole path BAM file -> ingest -> kernels -> <prefix>.results.json compared with the oracle."""
 import json
@@ -154,7 +154,7 @@ def test_error_texts_are_the_reference_s():
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     text = ""
-    for rel in ("ngs_amd/csrc/cli/ngs_main.cpp", "ngs_amd/csrc/cli/gff_loader.h", "ngs_amd/csrc/reference.cpp", "ngs_amd/csrc/bam_reader.cpp",
+    for rel in (*build.CLI_SOURCES, *build.CLI_HEADERS, "ngs_amd/csrc/reference.cpp", "ngs_amd/csrc/bam_reader.cpp",
                 "oracle/oracle.c", "oracle/histogram.c"):
         src = open(os.path.join(root, rel)).read()
         src = re.sub(r'"\s*\n\s*"', "", src)          # adjacent C string literals are one string

@@ -1,6 +1,7 @@
 """`ngs index` without a GPU: the test-side model (tests/bai_model.py) pinned on hand-worked cases
 and held against the project's other BAI writer (tests/bamio.py) on random sorted files, and the command line's
 refusals and messages, which all come before any GPU work."""
+import ctypes as C
 import os
 import struct
 import subprocess
@@ -202,9 +203,23 @@ def test_refuses_to_overwrite_an_existing_index(ngs, tmp_path):
     assert open(bam + ".bai", "rb").read() == before
 
 
-@pytest.mark.parametrize("order", ["unsorted", "queryname", "unknown", None])
-def test_requires_a_coordinate_sorted_header(ngs, tmp_path, order):
+def header_says_sorted(lib, path):
+    """ngsq_bam_sorted_by_coordinate of the file's header: the one answer the library and the command line share."""
+    bam = C.c_void_p()
+    assert lib.ngsq_bam_open(path.encode(), 0, C.byref(bam)) == 0, lib.ngsq_bam_last_error()
+    try:
+        return lib.ngsq_bam_sorted_by_coordinate(bam)
+    finally:
+        lib.ngsq_bam_close(bam)
+
+
+# ("coordinateX": the field is read as a whole, a header that only CONTAINS SO:coordinate is not sorted)
+@pytest.mark.parametrize("order", ["unsorted", "queryname", "unknown", "coordinateX", None])
+def test_requires_a_coordinate_sorted_header(ngs, lib, tmp_path, order):
     hb = index_sorted_batch(2, 50, weird=False)
+    good = str(tmp_path / "sorted.bam")
+    bamio.write_bam(good, hb, NAMES, LENS, with_index=False)
+    assert header_says_sorted(lib, good) == 1
     bam = str(tmp_path / "a.bam")
     bamio.write_bam(bam, hb, NAMES, LENS, with_index=False, sort_order=order or "coordinate")
     if order is None:   # no SO field at all
@@ -216,6 +231,7 @@ def test_requires_a_coordinate_sorted_header(ngs, tmp_path, order):
             for k in range(0, len(body), 60000):
                 f.write(bamio.bgzf_block(body[k:k + 60000]))
             f.write(bamio.EOF_BLOCK)
+    assert header_says_sorted(lib, bam) == 0
     r = run(ngs, "index", bam)
     assert r.returncode == 1 and "Error: the input BAM must be coordinate-sorted to be indexed" in r.stderr
     assert not os.path.exists(bam + ".bai")

@@ -4,7 +4,7 @@
   * the host C++ of the product that runs without a GPU -- the BGZF/BAM host reader and index reader
     (ngs_amd/csrc/bam_reader.cpp, bgzf.h) and the synthetic BAM writer (synth_bam.cpp) -- on well-formed files,
     on truncated / corrupted / crafted ones (incl. the extra-field subfield that used to be read past its end);
-  * the argument and early-error paths of the `ngs qc` command line (ngs_amd/csrc/cli/ngs_main.cpp) that end before
+  * the argument and early-error paths of the `ngs qc` command line (ngs_amd/csrc/cli/qc.cpp) that end before
     anything touches a GPU.
 Each check runs in a child process with the sanitizer runtime preloaded; a report on stderr or a non-zero exit fails."""
 import os
@@ -159,7 +159,7 @@ def test_cli_argument_paths_under_asan_ubsan(tmp_path):
     build.build(verbose=False)
     exe = str(tmp_path / "ngs_asan")
     lib_dir = os.path.join(ROOT, "ngs_amd")
-    subprocess.run(["g++", "-std=c++17", *SAN, os.path.join(lib_dir, "csrc", "cli", "ngs_main.cpp"), "-L" + lib_dir, "-lngsq",
+    subprocess.run(["g++", "-std=c++17", *SAN, *build.CLI_SOURCES, "-L" + lib_dir, "-lngsq",
                     "-Wl,-rpath," + lib_dir, "-Wl,-rpath-link,/opt/rocm/lib", "-lz", "-o", exe], check=True)
     hb = sorted_batch(1, 50)
     bam = str(tmp_path / "a.bam")

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """`ngs qc` of ONE BAM file on several GPUs of a node.  This is a launcher only: the work is
-`ngs qc --gpus N` (ngs_amd/csrc/cli/ngs_main.cpp): one worker process per GPU, each ingesting its BGZF
+`ngs qc --gpus N` (ngs_amd/csrc/cli/qc.cpp): one worker process per GPU, each ingesting its BGZF
 block range on its own device (ngsq_bam_shard_open), one ngsq_exchange over RCCL before the teardown
 (include/ngsq_comm.h), rank 0 writes <out>/<bam name>.results.json.
 
