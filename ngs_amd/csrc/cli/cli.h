@@ -1,6 +1,6 @@
 // cli.h -- what the commands of `ngs` share: the log, the error exit, option helpers, file-format sniffing, and the
-// reader plus facet-less context that `index` and `convert` walk a file with.  One file per command beside it: qc.cpp,
-// index.cpp, convert.cpp; ngs_main.cpp dispatches.  The command line includes the library's public headers only.
+// reader plus facet-less context that `index`, `convert` and `derive` walk a file with.  One file per command beside it:
+// qc.cpp, index.cpp, convert.cpp, derive.cpp; ngs_main.cpp dispatches.  The command line includes the library's public headers only.
 #pragma once
 
 #include <unistd.h>
@@ -23,6 +23,7 @@
 int qc_main(int argc, char **argv);
 int index_main(int argc, char **argv, int at);
 int convert_main(int argc, char **argv, int at);
+int derive_main(int argc, char **argv, int at);
 
 inline int g_level = 2; // 0 off (-q), 2 info (default), 3 debug (-v)   src/main.rs:71-83
 
@@ -151,7 +152,7 @@ inline std::string extension_of(const std::string &path) {
     return dot == std::string::npos ? "" : path.substr(dot + 1);
 }
 
-// A context without facets on `device` for the @SQ lengths of an open reader: what `index` and `convert` walk a file with.
+// A context without facets on `device` for the @SQ lengths of an open reader: what `index`, `convert` and `derive` walk a file with.
 // nullptr: no context (ngsq_last_global_error says why).
 inline ngsq_ctx *plain_context(const ngsq_bam *bam, int device) {
     const uint32_t n_refs = ngsq_bam_n_refs(bam);

@@ -277,7 +277,7 @@ bool parse_args(int argc, char **argv, Args *out, int *status) {
     }
     if (!saw_qc) {
         usage();
-        bail("this build provides the `qc`, `index` and `convert` subcommands only");
+        bail("this build provides the `qc`, `index`, `convert` and `derive instrument` subcommands only");
     }
     if (pos.size() != 2) {
         usage();

@@ -236,6 +236,16 @@ class SamReport(C.Structure):
                 ("total_ms", C.c_double)]
 
 
+# ---- include/ngsq_derive.h --------------------------------------------------------------------
+DERIVE_INSTRUMENTS, DERIVE_FLOWCELLS = 0, 1
+
+
+class DeriveReport(C.Structure):
+    _fields_ = [("records", C.c_uint64), ("skipped", C.c_uint64), ("instruments", C.c_uint64), ("flowcells", C.c_uint64),
+                ("entries", C.c_uint64), ("candidates", C.c_uint64), ("batches", C.c_uint64), ("scan_ms", C.c_double),
+                ("kernel_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 # ---- include/ngsq_comm.h ----------------------------------------------------------------------
 COMM_ID_BYTES = 128
 COMM_MAX_WORLD = 64
@@ -383,6 +393,15 @@ PROTOTYPES = {
     "ngsq_bam_build_index": (C.c_int, [C.c_void_p, ctx_p, C.c_char_p, C.POINTER(IndexReport)]),
     # include/ngsq_sam.h
     "ngsq_bam_write_sam": (C.c_int, [C.c_void_p, ctx_p, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(SamReport)]),
+    # include/ngsq_derive.h
+    "ngsq_bam_derive_instrument": (C.c_int, [C.c_void_p, ctx_p, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p),
+                                             C.POINTER(DeriveReport)]),
+    "ngsq_derive_names_count": (C.c_uint64, [C.c_void_p, C.c_int]),
+    "ngsq_derive_names_get": (C.c_void_p, [C.c_void_p, C.c_int, C.c_uint64, u32p]),
+    "ngsq_derive_names_free": (None, [C.c_void_p]),
+    "ngsq_derive_lookup": (C.c_int, [C.c_int, C.c_char_p, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ngsq_derive_predict": (C.c_int, [C.POINTER(C.c_char_p), u32p, C.c_uint64, C.POINTER(C.c_char_p), u32p, C.c_uint64, C.c_char_p,
+                                      C.c_size_t, C.POINTER(C.c_size_t)]),
     "ngsq_bgzf_inflate_device": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p, C.c_int]),
     # include/ngsq_comm.h
     "ngsq_comm_last_error": (C.c_char_p, [comm_p]),

@@ -559,3 +559,60 @@ def bam_to_sam(path: str, out_path: str, device: int = 0, max_records: int = 0, 
             return {k: getattr(rep, k) for k, _ in ffi.SamReport._fields_}
         finally:
             os.close(fd)
+
+
+def _c_strings(items: Sequence[bytes]):
+    """(char **, uint32_t *, n) for byte strings that may be empty or hold any byte; keep the result while they are in use."""
+    bufs = [C.create_string_buffer(bytes(x), len(x) + 1) for x in items]
+    ptrs = (C.c_char_p * max(len(bufs), 1))(*[C.cast(b, C.c_char_p) for b in bufs])
+    lens = (C.c_uint32 * max(len(bufs), 1))(*[len(x) for x in items])
+    return ptrs, lens, len(bufs), bufs
+
+
+def derive_lookup(which: int, query: bytes, lib=None) -> List[str]:
+    """The machines whose pattern `query` matches in the instrument table (which = ffi.DERIVE_INSTRUMENTS) or the flowcell
+    table (ffi.DERIVE_FLOWCELLS), ascending (include/ngsq_derive.h).  Host only."""
+    lib = lib or ffi.load_library()
+    need = C.c_size_t()
+    lib.ngsq_derive_lookup(which, query, len(query), None, 0, C.byref(need))
+    buf = C.create_string_buffer(need.value)
+    _check_bam(lib.ngsq_derive_lookup(which, query, len(query), buf, need.value, C.byref(need)), lib)
+    return buf.value.decode().split("\n")[:-1]
+
+
+def derive_predict(instruments: Sequence[bytes], flowcells: Sequence[bytes], lib=None) -> str:
+    """The document `ngs derive instrument` prints for these instrument ids and flowcell ids (include/ngsq_derive.h).  Host only."""
+    lib = lib or ffi.load_library()
+    pi, li, ni, keep_i = _c_strings(instruments)
+    pf, lf, nf, keep_f = _c_strings(flowcells)
+    need = C.c_size_t()
+    lib.ngsq_derive_predict(pi, li, ni, pf, lf, nf, None, 0, C.byref(need))
+    buf = C.create_string_buffer(need.value)
+    _check_bam(lib.ngsq_derive_predict(pi, li, ni, pf, lf, nf, buf, need.value, C.byref(need)), lib)
+    return buf.value.decode()
+
+
+def derive_instrument(path: str, device: int = 0, max_records: int = 0, batch_records: int = 0, table_slots: int = 0, lib=None):
+    """`ngs derive instrument` in process (include/ngsq_derive.h): the read names of `path` scanned on GPU `device` from the
+    device ingest.  max_records: examine at most this many records (0: all; the command line maps `-n N` to N + 1);
+    batch_records: records per ingest batch (0: the library's default); table_slots: slots of each set's device table (0: the
+    default).  Returns (instruments, flowcells, document, report): the two sets as sorted lists of bytes, the parsed
+    document, the report.  NgsqError on a name that is not an Illumina name."""
+    lib = lib or ffi.load_library()
+    with _reader_and_plain_context(lib, path, device) as (bam, ctx):
+        names = C.c_void_p()
+        rep = ffi.DeriveReport()
+        _check_bam(lib.ngsq_bam_derive_instrument(bam, ctx, max_records, batch_records, table_slots, C.byref(names), C.byref(rep)), lib)
+        try:
+            sets = []
+            for which in (ffi.DERIVE_INSTRUMENTS, ffi.DERIVE_FLOWCELLS):
+                got = []
+                for i in range(lib.ngsq_derive_names_count(names, which)):
+                    n = C.c_uint32()
+                    p = lib.ngsq_derive_names_get(names, which, i, C.byref(n))
+                    got.append(C.string_at(p, n.value) if n.value else b"")
+                sets.append(got)
+        finally:
+            lib.ngsq_derive_names_free(names)
+        doc = json.loads(derive_predict(sets[0], sets[1], lib))
+        return sets[0], sets[1], doc, {k: getattr(rep, k) for k, _ in ffi.DeriveReport._fields_}
