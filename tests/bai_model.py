@@ -5,7 +5,9 @@ virtual position behind the record in front of it (or behind the header) to the 
 byte, the start of the next block when that byte ends a block, empty or not -- and writes the index with the rules of
 section 12.1: reg2bin over the reference span (at least 1), a record's chunk merged into the last chunk of its bin only
 when that chunk ends where it starts, bins ascending, the metadata pseudo-bin 37450 last, the 16 kb linear index with the
-first record's chunk start per window and gaps carrying the value in front of them, n_no_coor at the end.
+first record's chunk start per window and gaps carrying the value in front of them, n_no_coor at the end.  A placed record
+the index cannot hold (include/ngsq_index.h: a sequence id outside the header, an end beyond 2^29, a window at or beyond
+ceil(LN / 16384) + 64) is refused, behind any order violation of the file.
 
 Nothing here calls the library: the GPU tests hold the device-built index against this."""
 from __future__ import annotations
@@ -25,6 +27,32 @@ class Unsorted(ValueError):
     def __init__(self, index: int):
         super().__init__(f"record {index} is out of coordinate order")
         self.index = index
+
+
+MAX_POS = 1 << 29      # the binning scheme's coordinate range (SAM specification 5.3)
+LIN_SLACK = 64         # 16 kb windows kept beyond @SQ LN: 1 Mbp
+
+
+class Limit(ValueError):
+    """A placed record the BAI cannot hold; .index is the first such record's index in the file."""
+
+    def __init__(self, index: int):
+        super().__init__(f"record {index} (0-based) cannot be held by a BAI: its sequence id is out of range, or it reaches "
+                         "beyond position 2^29 or more than 1 Mbp beyond its @SQ LN")
+        self.index = index
+
+
+def lin_cap(ln: int) -> int:
+    """The 16 kb windows kept for a sequence of length ln."""
+    return min((ln + 16383) // 16384 + LIN_SLACK, MAX_POS >> 14)
+
+
+def beyond_limit(r: "Rec", n_ref: int, ref_lens: Optional[Sequence[int]]) -> bool:
+    """The limit rule for a placed record (ref_lens None: the lengths are not known, only the first two rules apply)."""
+    end = r.pos + max(r.span, 1)
+    if r.ref >= n_ref or end > MAX_POS:
+        return True
+    return ref_lens is not None and (end - 1) >> 14 >= lin_cap(ref_lens[r.ref])
 
 
 def reg2bin(beg: int, end: int) -> int:
@@ -116,14 +144,22 @@ def _cg_tag(aux: bytes) -> Optional[List[int]]:
 
 def read_records(path: str) -> Tuple[List[Rec], int, List[str]]:
     """Every record of a BAM file with its chunk; the number of @SQ sequences; the header text."""
+    recs, lens, text = read_file(path)
+    return recs, len(lens), text
+
+
+def read_file(path: str) -> Tuple[List[Rec], List[int], List[str]]:
+    """Every record of a BAM file with its chunk; the lengths of the binary reference list; the header text."""
     blocks, s, size = read_blocks(path)
     assert s[:4] == b"BAM\1"
     l_text = struct.unpack_from("<i", s, 4)[0]
     text = s[8:8 + l_text].decode()
     n_ref = struct.unpack_from("<i", s, 8 + l_text)[0]
     p = 12 + l_text
+    lens = []
     for _ in range(n_ref):
         l_name = struct.unpack_from("<i", s, p)[0]
+        lens.append(struct.unpack_from("<i", s, p + 4 + l_name)[0])
         p += 8 + l_name
     recs: List[Rec] = []
     outs = [b.out for b in blocks]
@@ -143,11 +179,25 @@ def read_records(path: str) -> Tuple[List[Rec], int, List[str]]:
         recs.append(Rec(ref, pos, flag, _cigar_span(ops), prev_end, v1))
         prev_end = v1
         p = end
-    return recs, n_ref, text.splitlines()
+    return recs, lens, text.splitlines()
 
 
-def build(recs: Sequence[Rec], n_ref: int, meta: bool = True) -> bytes:
-    """The BAI bytes of records given in file order with their chunks.  Raises Unsorted."""
+def build(recs: Sequence[Rec], n_ref: int, meta: bool = True, ref_lens: Optional[Sequence[int]] = None) -> bytes:
+    """The BAI bytes of records given in file order with their chunks.  Raises Unsorted for the first record out of order,
+    and for a file in order Limit for the first record the index cannot hold (ref_lens: the @SQ lengths)."""
+    limit = None
+    last, seen_unplaced = None, False
+    for i, r in enumerate(recs):
+        if not (r.ref >= 0 and r.pos >= 0):
+            seen_unplaced = True
+            continue
+        if seen_unplaced or (last is not None and (r.ref, r.pos) < last):
+            raise Unsorted(i)
+        last = (r.ref, r.pos)
+        if limit is None and beyond_limit(r, n_ref, ref_lens):
+            limit = i
+    if limit is not None:
+        raise Limit(limit)
     bins: List[Dict[int, List[List[int]]]] = [dict() for _ in range(n_ref)]
     lin: List[Dict[int, int]] = [dict() for _ in range(n_ref)]
     stats = [None] * n_ref  # [ref_beg, ref_end, n_mapped, n_unmapped]
@@ -197,8 +247,8 @@ def build(recs: Sequence[Rec], n_ref: int, meta: bool = True) -> bytes:
 
 
 def expected_bai(path: str, meta: bool = True) -> bytes:
-    recs, n_ref, _ = read_records(path)
-    return build(recs, n_ref, meta)
+    recs, lens, _ = read_file(path)
+    return build(recs, len(lens), meta, lens)
 
 
 def parse(bai: bytes):

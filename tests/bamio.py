@@ -29,7 +29,7 @@ def reg2bin(beg: int, end: int) -> int:
     return 0
 
 
-def record_bytes(hb, i: int, name: bytes = b"r", aux: bytes = b"", full_name: bytes | None = None) -> bytes:
+def record_bytes(hb, i: int, name: bytes = b"r", aux: bytes = b"", full_name: bytes | None = None, mate_pos: int = -1) -> bytes:
     c = hb.cols
     l = int(c["l_seq"][i])
     if c["seq_off"] is not None:
@@ -50,9 +50,9 @@ def record_bytes(hb, i: int, name: bytes = b"r", aux: bytes = b"", full_name: by
     if len(cig) > 65535:   # SAM specification 4.2.2: the placeholder <l_seq>S<span>N in the CIGAR field, the operations in a CG:B,I tag
         aux = aux + aux_array(b"CG", b"I", np.asarray(cig, dtype="<u4").tobytes())
         cig = [(l << 4) | 4, (span << 4) | 3]
-    bin_ = reg2bin(pos, pos + max(span, 1)) if pos >= 0 else 4680   # (reg2bin(-1, 0), SAM specification 4.2.1)
+    bin_ = reg2bin(pos, pos + max(span, 1)) & 0xFFFF if pos >= 0 else 4680   # (reg2bin(-1, 0), SAM specification 4.2.1; beyond 2^29 the field cannot hold it)
     body = struct.pack("<iiBBHHHIiii", int(c["ref_id"][i]), pos, len(nm), int(c["mapq"][i]), bin_, len(cig),
-                       int(c["flag"][i]), l, int(c["mate_ref_id"][i]), -1, int(c["tlen"][i]))
+                       int(c["flag"][i]), l, int(c["mate_ref_id"][i]), mate_pos, int(c["tlen"][i]))
     body += nm + np.asarray(cig, dtype="<u4").tobytes() + seq + q + aux
     return struct.pack("<I", len(body)) + body
 
@@ -180,9 +180,14 @@ def adversarial_aux(rng, n_ref: int) -> bytes:
 
 
 def write_bam(path: str, hb, ref_names: Sequence[str], ref_len: Sequence[int], block_payload: int = 60000,
-              with_index: bool = True, sort_order: str = "coordinate", real_index: bool = False, names=None, aux=None) -> np.ndarray:
+              with_index: bool = True, sort_order: str = "coordinate", real_index: bool = False, names=None, aux=None,
+              level: int = 1, empty_members: float = 0.0, rng=None, mate_pos=None) -> np.ndarray:
     """names / aux: per record, the read name (without its NUL) and the auxiliary bytes behind the qualities (None: "r<i>",
     nothing -- the tag-less records of rounds 1-3).
+    mate_pos: per record, next_pos (None: -1 everywhere, the batch has no such column).
+    level: zlib's compression level of every block (0: stored blocks).  empty_members: the probability, drawn from `rng` per
+    record, that the block is ended in front of the record and an empty BGZF member (as the EOF marker is one) is put between
+    the two: the block's last byte then ends the record in front.
     Returns the records' BAM virtual offsets (block file offset << 16 | offset in the block's data): the ids the
     readers of include/ngsq_bam.h give them (ngsq_batch.record_id)."""
     text = f"@HD\tVN:1.6\tSO:{sort_order}\n" + "".join(f"@SQ\tSN:{n}\tLN:{l}\n" for n, l in zip(ref_names, ref_len))
@@ -191,25 +196,29 @@ def write_bam(path: str, hb, ref_names: Sequence[str], ref_len: Sequence[int], b
         head += struct.pack("<i", len(n) + 1) + n.encode() + b"\0" + struct.pack("<i", l)
     out: List[bytes] = []
     while len(head) > block_payload:  # a long header (thousands of @SQ lines) takes blocks of its own
-        out.append(bgzf_block(head[:block_payload]))
+        out.append(bgzf_block(head[:block_payload], level))
         head = head[block_payload:]
     cur = bytearray(head)
     rec_at = []  # (block number, offset in the block's data) of every record
     for i in range(hb.n):
-        rec = record_bytes(hb, i, aux=aux[i] if aux is not None else b"", full_name=names[i] if names is not None else None)
+        rec = record_bytes(hb, i, aux=aux[i] if aux is not None else b"", full_name=names[i] if names is not None else None,
+                           mate_pos=int(mate_pos[i]) if mate_pos is not None else -1)
+        if empty_members and cur and rng.random() < empty_members:
+            out += [bgzf_block(bytes(cur), level), bgzf_block(b"", level)]
+            cur = bytearray()
         if len(cur) >= block_payload:  # a record starts in the block that holds its first byte
-            out.append(bgzf_block(bytes(cur)))
+            out.append(bgzf_block(bytes(cur), level))
             cur = bytearray()
         rec_at.append((len(out), len(cur)))
         while len(cur) + len(rec) > block_payload:  # records may straddle blocks
             take = block_payload - len(cur)
             cur += rec[:take]
             rec = rec[take:]
-            out.append(bgzf_block(bytes(cur)))
+            out.append(bgzf_block(bytes(cur), level))
             cur = bytearray()
         cur += rec
     if cur:
-        out.append(bgzf_block(bytes(cur)))
+        out.append(bgzf_block(bytes(cur), level))
     out.append(EOF_BLOCK)
     with open(path, "wb") as f:
         f.write(b"".join(out))

@@ -2,9 +2,12 @@
 (tests/derive_model.py) exactly -- one name over many batches, thousands of records from dozens of instruments and flowcells
 with absent names, empty segments and the longest names, a table too small for them, thousands of names that are all new in
 one batch -- the first bad name is the one reported, the `-n` rule, an empty file, the hand-assembled files, a synthetic
-file, and the command line prints the model's document byte for byte."""
+file, and the command line prints the model's document byte for byte.  Files of several ingest chunks (the name of the record
+a chunk's end cuts is read from the carried bytes, a bad one copied out of them), and names first seen in the last lane of a
+launch, the first lane of the next, and both."""
 import ctypes as C
 import os
+import struct
 import subprocess
 
 import numpy as np
@@ -13,7 +16,9 @@ import pytest
 from ngs_amd import build, ffi, host
 from tests import bamio
 from tests import derive_model as dm
-from tests.util import random_batch
+from tests import sam_model as sm
+from tests.util import derive_check as check
+from tests.util import illumina, random_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -41,25 +46,6 @@ def write(path, names, seed=1, block_payload=60000):
     return path
 
 
-def illumina(rng, instrument: bytes, flowcell=None) -> bytes:
-    tail = b"%d:%d:%d:%d" % (rng.integers(1, 5), rng.integers(1101, 2679), rng.integers(1000, 32624), rng.integers(1000, 37000))
-    return instrument + (b":" + tail if flowcell is None else b":%d:" % rng.integers(1, 400) + flowcell + b":" + tail)
-
-
-def check(lib, path, n=0, **kw):
-    """The library's sets, document and counts against the model's for the first n (0: all) records' rule."""
-    lookup = lambda which, q: host.derive_lookup(which, q, lib)  # noqa: E731 (held to the fixture by tests/test_derive.py)
-    want_i, want_f, skipped, want_doc = dm.expected(path, n, lookup)
-    got_i, got_f, doc, rep = host.derive_instrument(path, max_records=n + 1 if n else 0, lib=lib, **kw)
-    assert got_i == want_i
-    assert got_f == want_f
-    assert doc == want_doc
-    assert rep["records"] == len(dm.examined(dm.read_names(path), n)) and rep["skipped"] == skipped
-    assert rep["instruments"] == len(want_i) and rep["flowcells"] == len(want_f)
-    assert rep["entries"] >= len(want_i) + len(want_f) and rep["candidates"] <= rep["entries"]
-    return doc, rep
-
-
 def test_one_instrument_over_many_batches(gpu_lib, tmp_path):
     rng = np.random.default_rng(31)
     path = write(str(tmp_path / "a.bam"), [bamio.aligner_name(rng) for _ in range(3000)])
@@ -70,15 +56,13 @@ def test_one_instrument_over_many_batches(gpu_lib, tmp_path):
     assert rep["entries"] <= 2 * 2
 
 
-@pytest.fixture(scope="module")
-def mixed(tmp_path_factory):
-    """20 000 records drawn from 40 instruments x 50 flowcells, with 5-segment names, absent names, empty segments, a 254-byte
-    name and an instrument of 200 bytes."""
-    rng = np.random.default_rng(32)
+def mixed_names(rng, n):
+    """n names drawn from 40 instruments x 50 flowcells, with 5-segment names, absent names, empty segments, an instrument of 200
+    bytes and, at index 7, the longest name: 254 bytes."""
     ins = [b"A%05d" % rng.integers(0, 100000) for _ in range(30)] + [b"HWI-ST%d" % rng.integers(100, 100000) for _ in range(9)] + [b"x" * 200]
     fcs = [b"H" + bytes(rng.choice(list(b"ABCXYZ0123456789"), 5).tolist()) + b"SXX" for _ in range(49)] + [b""]
     names = []
-    for k in range(20000):
+    for _ in range(n):
         r = rng.random()
         if r < 0.02:
             names.append(b"*")
@@ -88,7 +72,16 @@ def mixed(tmp_path_factory):
             names.append(illumina(rng, ins[rng.integers(0, 40)]))
         else:
             names.append(illumina(rng, ins[rng.integers(0, 40)], fcs[rng.integers(0, 50)]))
-    names[7] = (b"K00321:9:" + b"F" * 254)[:254 - 8] + b":1:2:3:4"                  # the longest name: 254 bytes
+    names[7] = (b"K00321:9:" + b"F" * 254)[:254 - 8] + b":1:2:3:4"
+    return names
+
+
+@pytest.fixture(scope="module")
+def mixed(tmp_path_factory):
+    """20 000 records drawn from 40 instruments x 50 flowcells, with 5-segment names, absent names, empty segments, a 254-byte
+    name and an instrument of 200 bytes."""
+    rng = np.random.default_rng(32)
+    names = mixed_names(rng, 20000)
     names[12345] = b"y" * 200 + b":1:2:3:" + b"9" * 47                            # 254 bytes again, 5 segments
     assert len(names[7]) == 254 and len(names[12345]) == 254 and names[7].count(b":") == 6
     path = str(tmp_path_factory.mktemp("derive") / "mixed.bam")
@@ -172,6 +165,91 @@ def test_num_records_examines_one_more(gpu_lib, tmp_path):
     assert rep["records"] == 2000 and rep["instruments"] == 3
     _, rep = check(gpu_lib, path, n=1)
     assert rep["records"] == 2
+
+
+def write_long(path, names, seed=43):
+    """Records of 1 000 to 20 000 bases with an aligner's tags: 16 kB each, half a MiB of them per 1 MiB ingest buffer."""
+    rng = np.random.default_rng(seed)
+    hb = random_batch(rng, len(names), LENS, max_len=20_000, min_len=1000, weird=False)
+    aux = [bamio.aligner_aux(rng, int(hb.cols["l_seq"][i])) for i in range(hb.n)]
+    bamio.write_bam(path, hb, NAMES, LENS, names=names, aux=aux, with_index=False)
+    return path
+
+
+@pytest.fixture(scope="module")
+def mixed_long(tmp_path_factory):
+    names = mixed_names(np.random.default_rng(42), 260)
+    return write_long(str(tmp_path_factory.mktemp("derive_long") / "long.bam"), names), names
+
+
+def batch_sizes(lib, path):
+    """The records of the device ingest's successive batches, each as large as the chunk allows."""
+    sizes = []
+    with host._reader_and_plain_context(lib, path, 0) as (bam, ctx):
+        while True:
+            bt = ffi.Batch()
+            assert lib.ngsq_bam_next_batch_device(bam, ctx, 1 << 22, C.byref(bt)) == 0, lib.ngsq_bam_last_error()
+            if not bt.n_records:
+                return sizes
+            sizes.append(int(bt.n_records))
+
+
+def test_files_of_several_ingest_chunks(gpu_lib, mixed_long, monkeypatch):
+    monkeypatch.setenv("NGSQ_INGEST_RAW_MB", "1")
+    path, names = mixed_long
+    inflated = len(dm.bai_model.read_blocks(path)[1])
+    assert inflated > 7 << 19
+    _, rep = check(gpu_lib, path)
+    assert rep["batches"] >= inflated // 2 ** 20 and rep["batches"] >= 4 and rep["records"] == len(names)
+    _, two = check(gpu_lib, path, table_slots=2)
+    assert two["batches"] == rep["batches"] and two["candidates"] > 0
+
+
+@pytest.mark.parametrize("which", [1, -1])
+def test_a_bad_name_in_the_record_a_chunk_s_end_cuts(gpu_lib, mixed_long, tmp_path, monkeypatch, which):
+    """The first record of every batch but the first is the one the end of the chunk in front cut: its bytes lie in front of
+    the chunk's own, and the message's name is copied out of them."""
+    monkeypatch.setenv("NGSQ_INGEST_RAW_MB", "1")
+    path, names = mixed_long
+    sizes = batch_sizes(gpu_lib, path)
+    assert len(sizes) >= 4 and sum(sizes) == len(names)
+    cut = np.cumsum(sizes)[:-1]                                   # the first record of batches 1 ..
+    at = int(cut[0 if which > 0 else -1])
+    # the record does straddle a block boundary (a chunk ends on one): it is the cut record, not one that happens to come first
+    blocks, stream, _ = dm.bai_model.read_blocks(path)
+    _, _, _, p = sm.read_bam(path)
+    for _ in range(at):
+        p += 4 + struct.unpack_from("<I", stream, p)[0]
+    end = p + 4 + struct.unpack_from("<I", stream, p)[0]
+    assert any(p < b.out < end for b in blocks)
+    bad = list(names)
+    bad[at] = b"x" if names[at] == b"*" else names[at].replace(b":", b"_")       # one segment, as many bytes: the same chunks
+    planted = write_long(str(tmp_path / "cut.bam"), bad)
+    assert batch_sizes(gpu_lib, planted) == sizes
+    with pytest.raises(dm.BadName) as want:
+        dm.expected(planted)
+    assert want.value.name == bad[at]
+    with pytest.raises(host.NgsqError) as e:
+        host.derive_instrument(planted, lib=gpu_lib)
+    assert e.value.code == ffi.ERR_INVALID_ARGUMENT and str(e.value).endswith(str(want.value))
+    got = host.derive_instrument(planted, max_records=at, lib=gpu_lib)           # short of it: fine
+    assert got[3]["records"] == at
+
+
+@pytest.mark.parametrize("B", [63, 64, 65, 255, 256, 257])
+def test_names_first_seen_at_the_edges_of_waves_blocks_and_launches(gpu_lib, tmp_path, B):
+    """Batches of B records: a new instrument in the last lane of the first launch, another in the first lane of the second, a
+    fourth in the last lane of the second and the first lane of the third at once."""
+    rng = np.random.default_rng(44)
+    names = [illumina(rng, b"A00741", b"HG7WKDSXX") for _ in range(4 * B)]
+    names[B - 1] = illumina(rng, b"D00123", b"HG7WKDSXX")
+    names[B] = illumina(rng, b"E00456", b"HG7WKDSXX")
+    names[2 * B - 1] = illumina(rng, b"M01234", b"HG7WKDSXX")
+    names[2 * B] = illumina(rng, b"M01234", b"HG7WKDSXX")
+    path = write(str(tmp_path / "w.bam"), names, seed=45)
+    _, rep = check(gpu_lib, path, batch_records=B)
+    assert rep["records"] == 4 * B and rep["batches"] == 4
+    assert rep["instruments"] == 4 and rep["flowcells"] == 1 and rep["entries"] >= 5
 
 
 def test_header_only_file(gpu_lib, tmp_path):

@@ -2,6 +2,7 @@
 and held against the project's other BAI writer (tests/bamio.py) on random sorted files, and the command line's
 refusals and messages, which all come before any GPU work."""
 import ctypes as C
+import hashlib
 import os
 import struct
 import subprocess
@@ -37,11 +38,12 @@ def reorder(hb, order):
     return host.HostBatch(len(order), cols, 0, 0, 0, 0)
 
 
-def index_sorted_batch(seed, n, lens=LENS, weird=True):
+def index_sorted_batch(seed, n, lens=LENS, weird=True, max_len=150, min_len=1):
     """Random records (every flag, every CIGAR op, empty CIGARs, reads beyond LN) in coordinate order: placed records by
-    (sequence, position), the unplaced ones (no sequence or no position) behind them."""
-    rng = np.random.default_rng(seed)
-    hb = random_batch(rng, n, lens, max_len=150, min_len=1, weird=weird)
+    (sequence, position), the unplaced ones (no sequence or no position) behind them.  seed: an integer, or a generator to
+    draw from."""
+    rng = seed if isinstance(seed, np.random.Generator) else np.random.default_rng(seed)
+    hb = random_batch(rng, n, lens, max_len=max_len, min_len=min_len, weird=weird)
     c = hb.cols
     unplaced = (c["ref_id"] < 0) | (c["pos"] < 0)
     order = np.lexsort((np.arange(n), c["pos"], c["ref_id"], unplaced))
@@ -149,6 +151,54 @@ def test_hand_spec_empty_member_separates_chunk_and_record_id():
     assert any(r.v0 in empty for r in recs)
 
 
+# ---- the limit rule (include/ngsq_index.h; the message of bai.cpp) -----------------------------------------------------------
+
+def test_window_limit_both_sides_of_the_edge():
+    # LN 300 000: ceil(300000 / 16384) = 19 windows of the sequence, 64 of slack: windows 0 .. 82 are kept, [0, 83 * 16384)
+    assert bm.lin_cap(300_000) == 83 and 83 * 16384 == 1_359_872
+    assert bm.lin_cap(16384) == 65 and bm.lin_cap(16385) == 66 and bm.lin_cap(1) == 65
+    ok = chain([(0, 100, 50, 0), (0, 1_359_872 - 10, 10, 0), (1, 5, 5, 0)])      # last base 1 359 871: window 82
+    (_, lin), (_, lin1) = bm.parse(bm.build(ok, 2, ref_lens=[300_000, 70_000]))[0]
+    assert len(lin) == 83 and lin[82] == ok[1].v0 and lin[81] == ok[0].v0 and lin1 == [ok[2].v0]
+    with pytest.raises(bm.Limit) as e:
+        bm.build(chain([(0, 100, 50, 0), (0, 1_359_872 - 10, 11, 0), (1, 5, 5, 0)]), 2, ref_lens=[300_000, 70_000])
+    assert e.value.index == 1 and "record 1 (0-based) cannot be held by a BAI" in str(e.value)
+    with pytest.raises(bm.Limit):                                                   # a span of 0 counts as one base
+        bm.build(chain([(0, 1_359_872, 0, 0)]), 1, ref_lens=[300_000])
+    bm.build(chain([(0, 1_359_871, 0, 0)]), 1, ref_lens=[300_000])
+    # an N skip reaches there with a short read: 5M 1359000N 5M from 862 ends at 1 359 872
+    bm.build(chain([(0, 862, 5 + 1_359_000 + 5, 0)]), 1, ref_lens=[300_000])
+    with pytest.raises(bm.Limit):
+        bm.build(chain([(0, 863, 5 + 1_359_000 + 5, 0)]), 1, ref_lens=[300_000])
+
+
+def test_position_limit_both_sides_of_2_to_the_29():
+    # LN 2^29: 32768 windows and no slack beyond the binning scheme's range
+    assert bm.lin_cap(1 << 29) == 32768 and bm.lin_cap((1 << 29) - 20_000) == 32768 and bm.lin_cap(1 << 31) == 32768
+    ok = chain([(0, (1 << 29) - 7, 7, 0)])
+    (bins, lin), = bm.parse(bm.build(ok, 1, ref_lens=[1 << 29]))[0]
+    assert len(lin) == 32768 and lin[32767] == ok[0].v0 and lin[32766] == 0 and 4681 + 32767 in bins
+    for bad in ([(0, (1 << 29) - 7, 8, 0)], [(0, 1 << 29, 0, 0)], [(0, 10, 1 << 29, 0)]):
+        with pytest.raises(bm.Limit) as e:
+            bm.build(chain(bad), 1, ref_lens=[1 << 29])
+        assert e.value.index == 0
+    with pytest.raises(bm.Limit):                                                   # without the lengths the rule still holds
+        bm.build(chain([(0, (1 << 29) - 7, 8, 0)]), 1)
+
+
+def test_sequence_id_limit_and_the_first_record_is_named():
+    bm.build(chain([(0, 1, 1, 0), (1, 1, 1, 0)]), 2, ref_lens=[100, 100])
+    with pytest.raises(bm.Limit) as e:
+        bm.build(chain([(0, 1, 1, 0), (1, 1, 1, 0), (2, 1, 1, 0), (2, 2, 1 << 29, 0)]), 2, ref_lens=[100, 100])
+    assert e.value.index == 2
+    # an unplaced record is never refused, whatever its fields say
+    bm.build(chain([(0, 1, 1, 0), (-1, 1 << 30, 1 << 30, 4), (7, -1, 5, 4)]), 2, ref_lens=[100, 100])
+    # an order violation anywhere in the file comes first, as the library reports it
+    with pytest.raises(bm.Unsorted) as u:
+        bm.build(chain([(0, 10, 1 << 29, 0), (0, 20, 1, 0), (0, 15, 1, 0)]), 1, ref_lens=[100])
+    assert u.value.index == 2
+
+
 # ---- the model against tests/bamio.py's writer -------------------------------------------------------------------------
 
 @pytest.mark.parametrize("seed,n,payload", [(1, 400, 60000), (2, 3000, 4000), (3, 2000, 997), (4, 1, 60000), (5, 800, 300)])
@@ -171,6 +221,38 @@ def test_model_equals_bamio_writer_without_the_pseudo_bin(tmp_path, seed, n, pay
             continue
         unm = int(((c["flag"] & 4) != 0)[sel].sum())
         assert meta[1] == (int(sel.sum()) - unm, unm)
+
+
+def test_default_files_of_the_writer_are_unchanged_by_its_new_options(tmp_path):
+    """`level`, `empty_members`: a file written with the defaults has the bytes it had before the writer knew them (the
+    SHA-256 values were taken from the writer as it was, on test_bamio_files_equal_the_model's recipe)."""
+    before = {(11, 5000, 60000): "e07da266c2e6a280a58982b06e70eecbf4dbd0f1d53ef22a7868fc016c333342",
+              (13, 3000, 500): "476451355f42ccda718c37978e1288f21dc8a2cee3cb1200a213481cdf7d7f6d"}
+    for (seed, n, payload), want in before.items():
+        path = str(tmp_path / "r.bam")
+        bamio.write_bam(path, index_sorted_batch(seed, n), NAMES, LENS, block_payload=payload, with_index=False)
+        assert hashlib.sha256(open(path, "rb").read()).hexdigest() == want
+
+
+def test_writer_options_change_the_framing_only(tmp_path):
+    hb = index_sorted_batch(6, 500)
+    plain, opt = str(tmp_path / "a.bam"), str(tmp_path / "b.bam")
+    va = bamio.write_bam(plain, hb, NAMES, LENS, block_payload=900, with_index=False)
+    vb = bamio.write_bam(opt, hb, NAMES, LENS, block_payload=900, with_index=False, level=0, empty_members=0.3,
+                         rng=np.random.default_rng(6))
+    ba, sa, _ = bm.read_blocks(plain)
+    bb, sb, _ = bm.read_blocks(opt)
+    assert sa == sb and len(bb) > len(ba) + 10 and sum(b.isize == 0 for b in ba) == 1
+    ends, p = set(), int(vb[0]) & 0xFFFF
+    while p < len(sb):
+        p += 4 + struct.unpack_from("<I", sb, p)[0]
+        ends.add(p)
+    assert all(bb[k].out in ends and bb[k - 1].isize for k in range(1, len(bb) - 1) if bb[k].isize == 0)   # each one behind a record
+    # a record's id is the block that holds its first byte, never an empty member in front of it
+    empty = {b.coff for b in bb if b.isize == 0}
+    assert not {int(v) >> 16 for v in vb} & empty and len(vb) == len(va) == hb.n
+    starts = {b.coff: b.out for b in bb}
+    assert sorted(ends | {int(vb[0]) & 0xFFFF}) == sorted({starts[int(v) >> 16] + (int(v) & 0xFFFF) for v in vb} | {len(sb)})
 
 
 def test_model_rejects_the_unsorted_file(tmp_path):

@@ -310,3 +310,51 @@ def coordinate_sorted(hb: HostBatch) -> HostBatch:
     ref = hb.cols["ref_id"].astype(np.int64)
     key = np.where(ref < 0, np.int64(1) << 40, ref << 32 | (hb.cols["pos"].astype(np.int64) + 1))
     return take_records(hb, np.argsort(key, kind="stable"))
+
+
+def derive_check(lib, path, n=0, **kw):
+    """`ngs derive instrument` in process against tests/derive_model.py: the library's sets, document and counts against the
+    model's for the first n (0: all) records' rule.  Returns (document, report)."""
+    from ngs_amd import host
+    from tests import derive_model as dm
+    lookup = lambda which, q: host.derive_lookup(which, q, lib)  # noqa: E731 (held to the fixture by tests/test_derive.py)
+    want_i, want_f, skipped, want_doc = dm.expected(path, n, lookup)
+    got_i, got_f, doc, rep = host.derive_instrument(path, max_records=n + 1 if n else 0, lib=lib, **kw)
+    assert got_i == want_i
+    assert got_f == want_f
+    assert doc == want_doc
+    assert rep["records"] == len(dm.examined(dm.read_names(path), n)) and rep["skipped"] == skipped
+    assert rep["instruments"] == len(want_i) and rep["flowcells"] == len(want_f)
+    assert rep["entries"] >= len(want_i) + len(want_f) and rep["candidates"] <= rep["entries"]
+    return doc, rep
+
+
+def illumina(rng, instrument: bytes, flowcell=None) -> bytes:
+    """An Illumina read name of five segments (instrument:lane:tile:x:y), or seven with a flowcell (instrument:run:flowcell:...)."""
+    tail = b"%d:%d:%d:%d" % (rng.integers(1, 5), rng.integers(1101, 2679), rng.integers(1000, 32624), rng.integers(1000, 37000))
+    return instrument + (b":" + tail if flowcell is None else b":%d:" % rng.integers(1, 400) + flowcell + b":" + tail)
+
+
+def plant(rng, kind, n_refs=3):
+    """(record dict overrides, aux bytes) of one record without SAM text, and the error code tests/sam_model.py gives it."""
+    import struct
+    from tests import bamio
+    from tests import sam_model as sm
+    if kind == "tag_type":
+        return {}, b"NMC\x01XXq\x01\x02\x03", sm.E_TAG_TYPE
+    if kind == "z_nul":
+        return {}, b"NMC\x01XZZno terminator", sm.E_STR_NUL
+    if kind == "h_nul":
+        return {}, b"XHH0AFF", sm.E_STR_NUL
+    if kind == "b_sub":
+        return {}, b"XBBq" + struct.pack("<I", 1) + b"\0", sm.E_B_SUB
+    if kind == "b_count":
+        return {}, b"XBBi" + struct.pack("<I", 1000) + b"\0" * 16, sm.E_OVERRUN
+    if kind == "qual":
+        return {"qual": [30, 40, 94, 20]}, b"", sm.E_QUAL
+    if kind == "cigar_op":
+        return {"cigar": [(2 << 4) | 0, (2 << 4) | 9]}, b"", sm.E_CIGAR_OP
+    if kind.startswith("ref:"):     # a sequence id outside [-1, n_refs)
+        return {"ref:id_n_refs": {"ref_id": n_refs}, "ref:id_minus_2": {"ref_id": -2}, "ref:mate_n_refs": {"mate_ref_id": n_refs},
+                "ref:mate_int_max": {"mate_ref_id": 2 ** 31 - 1}}[kind], bamio.aux_z(b"RG", b"g1"), sm.E_REF
+    raise ValueError(kind)

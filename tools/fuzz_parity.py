@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
-"""Randomised parity sweep (GPU): many seeds / shapes through the facet kernels against the oracle, and
-through file -> device ingest -> kernels against file -> host ingest -> kernels.  Not part of pytest:
+"""Randomised parity sweep (GPU): many seeds / shapes through the facet kernels against the oracle, through
+file -> device ingest -> kernels against file -> host ingest -> kernels, and through the ingest's consumers (`ngs convert`,
+`ngs derive instrument`, `ngs index`) against their test-side models.  Not part of pytest:
     python tools/fuzz_parity.py [--seeds 40]
 """
 import argparse
 import ctypes as C
 import os
+import shutil
 import sys
 import tempfile
 
@@ -223,6 +225,179 @@ def genome_sweep(lib, seeds, base=0):
     print("genome sweep ok")
 
 
+SAM_PLANTS = ["tag_type", "z_nul", "h_nul", "b_sub", "b_count", "qual", "cigar_op"]
+NAME_PLANTS = [b"read/1", b"A00741:215:HG7WKDSXX:1:1101:1000", b"A00741:215:HG7WKDSXX:1:1101:1000:2000:extra"]   # 1, 6, 8 segments
+
+
+def _concat(parts):
+    """HostBatches (offsets layout) one behind the other."""
+    cols = {k: np.concatenate([p.cols[k] for p in parts]) for k in host.FIXED_COLUMNS}
+    for data, off in (("seq", "seq_off"), ("qual", "qual_off"), ("cigar", "cigar_off")):
+        cols[data] = np.concatenate([p.cols[data] for p in parts])
+        lens = np.concatenate([np.diff(p.cols[off].astype(np.int64)) for p in parts])
+        cols[off] = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+    return host.HostBatch(sum(p.n for p in parts), cols, 0, 0, 0, 0)
+
+
+def consumer_case(seed, dir):
+    """One BAM file for the consumers sweep and what the sweep does with it; pure CPU, no library call.  Everything is drawn from
+    default_rng(15000 + seed): records of 1 base to 100 kb in coordinate order (3-6 MiB of them inflated, 30 000 at most: several
+    ingest chunks of 1 MiB, a few of 4), Illumina names from a pool of instruments and flowcells with the odd ones of the derive
+    tests, aligner / adversarial / no tags in a per-seed ratio, float tags on none to all of the records, blocks of 0.7-60 kB at
+    zlib level 0, 1 or 6 with empty members in between.  seed % 4 == 1: one record without SAM text; seed % 4 == 3: one name that
+    is no Illumina name.  Returns a dict: path, n, inflated (bytes), chunk_mb (None: the default), batch_records, table_slots,
+    max_records, sam_plant (index, kind) / name_plant (index, name) or None, and the parameters it prints."""
+    from tests.test_index import LENS, NAMES, index_sorted_batch
+    from tests.util import batch_from_records, illumina, plant
+    rng = np.random.default_rng(15000 + seed)
+    max_len = int(rng.choice([1, 3, 36, 150, 151, 1000, 20_000, 100_000]))
+    uniform = bool(rng.random() < 0.4)
+    min_len = max_len if uniform else int(rng.integers(1, max_len + 1))
+    weird = bool(rng.integers(0, 2))
+    mix = rng.dirichlet([1.0, 1.0, 1.0])                          # aligner : adversarial : no tags
+    float_share = float(rng.choice([0.0, 0.01, 0.5, 1.0]))
+    est = 36 + 4 + 40 + 8 + 1.5 * (min_len + max_len) / 2 + 80 * mix[0] + 110 * mix[1] + float_share * 420
+    n = int(max(1, min(30_000, 4.5 * 2 ** 20 / est)))
+    hb = index_sorted_batch(rng, n, LENS, weird=weird, max_len=max_len, min_len=min_len)
+    # names: the `mixed` recipe of tests/test_derive_gpu.py, shrunk
+    ins = [b"A%05d" % rng.integers(0, 100000) for _ in range(int(rng.integers(1, 41)))]
+    fcs = [b"H" + bytes(rng.choice(list(b"ABCXYZ0123456789"), 5).tolist()) + b"SXX" for _ in range(int(rng.integers(1, 51)))]
+    if rng.random() < 0.5:
+        fcs.append(b"")
+    names = []
+    for _ in range(n):
+        r = rng.random()
+        if r < 0.01:
+            names.append(b"*")
+        elif r < 0.02:
+            names.append(b"::::" if r < 0.015 else b"::::::")
+        elif r < 0.2:
+            names.append(illumina(rng, ins[rng.integers(0, len(ins))]))
+        else:
+            names.append(illumina(rng, ins[rng.integers(0, len(ins))], fcs[rng.integers(0, len(fcs))]))
+    long_at = int(rng.integers(0, n))
+    names[long_at] = (b"K00321:9:" + b"F" * 254)[:254 - 8] + b":1:2:3:4"
+    aux = []
+    for i in range(n):
+        a = b""
+        if rng.random() < float_share:
+            bits = rng.integers(0, 2 ** 32, int(rng.integers(1, 201)), dtype=np.uint64).astype("<u4")
+            a += b"Xff" + bits[:1].tobytes() + bamio.aux_array(b"ZF", b"f", bits.tobytes())
+        k = rng.random()
+        if k < mix[0]:
+            a += bamio.aligner_aux(rng, int(hb.cols["l_seq"][i]))
+        elif k < mix[0] + mix[1]:
+            a += bamio.adversarial_aux(rng, len(NAMES))
+        aux.append(a)
+    sam_plant = name_plant = None
+    if seed % 4 == 1:
+        at, kind = int(rng.integers(0, n)), SAM_PLANTS[int(rng.integers(0, len(SAM_PLANTS)))]
+        over, bad_aux, _code = plant(rng, kind)
+        c = hb.cols
+        rec = dict(flag=0, mapq=60, ref_id=int(c["ref_id"][at]), pos=int(c["pos"][at]), mate_ref_id=int(c["mate_ref_id"][at]), tlen=0,
+                   cigar="4M", seq="ACGT", qual=[30, 31, 32, 33])
+        rec.update(over)
+        hb = _concat([hb.slice(0, at), batch_from_records([rec]), hb.slice(at + 1, n)])
+        aux[at] = bad_aux
+        if at == long_at or names[at].count(b":") not in (4, 6):
+            names[at] = illumina(rng, ins[0], fcs[0])
+        sam_plant = (at, kind)
+    elif seed % 4 == 3:
+        at = int(rng.integers(0, n))
+        names[at] = NAME_PLANTS[int(rng.integers(0, 3))]
+        name_plant = (at, names[at])
+    payload, level = int(rng.choice([700, 4000, 60000])), int(rng.choice([0, 1, 6]))
+    empty_p = float(rng.choice([0.0, 0.02, 0.3]))
+    path = os.path.join(dir, f"consumers_{seed}.bam")
+    bamio.write_bam(path, hb, NAMES, LENS, block_payload=payload, with_index=False, names=names, aux=aux, level=level,
+                    empty_members=empty_p, rng=rng)
+    batch_records = int(rng.choice([63, 64, 65, 257, 2500, 0]))
+    table_slots = int(rng.choice([0, 2, 16, 1024]))
+    max_records = 0 if rng.random() < 2 / 3 else int(rng.integers(2, n + 6))
+    from tests import bai_model as bm
+    inflated = sum(b.isize for b in bm.read_blocks(path)[0])
+    return dict(path=path, n=n, inflated=inflated, chunk_mb=(1, 4, None)[seed % 3], batch_records=batch_records, table_slots=table_slots,
+                max_records=max_records, sam_plant=sam_plant, name_plant=name_plant, max_len=max_len, uniform=uniform, payload=payload,
+                level=level, empty_members=empty_p, float_share=float_share)
+
+
+def consumers_sweep(lib, seeds, base=0):
+    """`ngs convert`, `ngs derive instrument` and `ngs index` in process against tests/sam_model.py, tests/derive_model.py and
+    tests/bai_model.py on the files of consumer_case: byte for byte, set for set, and the planted record's message."""
+    from tests import bai_model as bm
+    from tests import derive_model as dm
+    from tests import sam_model as sm
+    from tests.util import derive_check
+    td = tempfile.mkdtemp(prefix="ngsq_fuzz_consumers_")
+    for seed in range(base, base + seeds):
+        case = consumer_case(seed, td)
+        path, m = case["path"], case["max_records"]
+        if case["chunk_mb"] is None:
+            os.environ.pop("NGSQ_INGEST_RAW_MB", None)
+        else:
+            os.environ["NGSQ_INGEST_RAW_MB"] = str(case["chunk_mb"])
+        crossed = case["chunk_mb"] == 1 and m == 0
+        # convert
+        out = os.path.join(td, "out.sam")
+        try:
+            want = sm.expected_sam(path, m)
+        except sm.SamError as e:
+            want = e
+        if isinstance(want, sm.SamError):
+            try:
+                host.bam_to_sam(path, out, max_records=m, batch_records=case["batch_records"], lib=lib)
+            except host.NgsqError as e:
+                assert want.message in str(e), (seed, want.message, str(e))
+            else:
+                raise AssertionError(f"seed {seed}: convert wrote a file, the model says: {want.message}")
+            sam = "error as the model's"
+        else:
+            rep = host.bam_to_sam(path, out, max_records=m, batch_records=case["batch_records"], lib=lib)
+            got = open(out, "rb").read()
+            if got != want:
+                gl, wl = got.split(b"\n"), want.split(b"\n")
+                k = next((k for k, (a, b) in enumerate(zip(gl, wl)) if a != b), min(len(gl), len(wl)))
+                raise AssertionError(f"seed {seed}: SAM line {k} of {len(gl)} / {len(wl)}:\n got  {gl[k:k + 1]!r:.400}\n want {wl[k:k + 1]!r:.400}")
+            assert rep["records"] == (min(m, case["n"]) if m else case["n"]), (seed, rep)
+            if crossed:     # a batch ends where a chunk ends, and the variable caps a chunk's inflated bytes
+                assert rep["batches"] >= case["inflated"] // 2 ** 20, (seed, rep["batches"], case["inflated"])
+            sam = f"{rep['batches']} batches"
+        # derive (max_records m examines m records: the model's rule for -n m - 1)
+        kw = dict(batch_records=case["batch_records"], table_slots=case["table_slots"])
+        try:
+            dm.collect(dm.examined(dm.read_names(path), m - 1 if m else 0))
+            bad = None
+        except dm.BadName as e:
+            bad = str(e)
+        if bad is not None:
+            try:
+                host.derive_instrument(path, max_records=m, lib=lib, **kw)
+            except host.NgsqError as e:
+                assert str(e).endswith(bad), (seed, bad, str(e))
+            else:
+                raise AssertionError(f"seed {seed}: derive succeeded, the model says: {bad}")
+            der = "error as the model's"
+        else:
+            _, rep = derive_check(lib, path, m - 1 if m else 0, **kw)
+            if crossed:
+                assert rep["batches"] >= case["inflated"] // 2 ** 20, (seed, rep["batches"], case["inflated"])
+            der = f"{rep['instruments']} + {rep['flowcells']} names in {rep['batches']} batches"
+        # index (the whole file, whatever was planted for the other two)
+        rep = host.build_bam_index(path, lib=lib)
+        assert open(path + ".bai", "rb").read() == bm.expected_bai(path), f"seed {seed}: the index differs from the model's"
+        assert rep["records"] == case["n"] and lib.ngsq_bam_check_index(path.encode()) == 0, (seed, rep)
+        for f in (path, path + ".bai", out):
+            os.remove(f)
+        planted = f"sam {case['sam_plant']}" if case["sam_plant"] else f"name {case['name_plant'][0]}" if case["name_plant"] else "none"
+        print(f"consumers seed {seed}: n={case['n']} max_len={case['max_len']} uniform={case['uniform']} inflated={case['inflated']} "
+              f"chunk={case['chunk_mb'] or 'default'} MiB payload={case['payload']} level={case['level']} empty={case['empty_members']} "
+              f"floats={case['float_share']} batch={case['batch_records']} slots={case['table_slots']} max_records={m} planted={planted}: "
+              f"convert {sam}, derive {der}, index {rep['runs']} runs ok", flush=True)
+    os.environ.pop("NGSQ_INGEST_RAW_MB", None)
+    shutil.rmtree(td)            # (a failing seed leaves its file there)
+    print("consumers sweep ok")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--genome", type=int, default=0, help="seeds of the many-sequences sweep (all seven facets, up to 200 @SQ)")
@@ -230,6 +405,7 @@ def main():
     ap.add_argument("--seeds", type=int, default=40)
     ap.add_argument("--sorted", type=int, default=0, help="seeds of the sorted_input (streaming Coverage) sweep")
     ap.add_argument("--ingest", type=int, default=0, help="seeds of the device-reader-against-host-reader sweep")
+    ap.add_argument("--consumers", type=int, default=0, help="seeds of the convert / derive / index sweep against their models")
     ap.add_argument("--seed-base", type=int, default=0, help="first seed of every sweep (a soak behind an earlier one takes up where that left off)")
     a = ap.parse_args()
     lib = ffi.load_library()
@@ -241,6 +417,8 @@ def main():
         extra_sweep(lib, a.extra, a.seed_base)
     if a.ingest:
         ingest_sweep(lib, a.ingest, a.seed_base)
+    if a.consumers:
+        consumers_sweep(lib, a.consumers, a.seed_base)
     td = tempfile.mkdtemp(prefix="ngsq_fuzz_")
     for seed in range(a.seed_base, a.seed_base + a.seeds):
         rng = np.random.default_rng(1000 + seed)
