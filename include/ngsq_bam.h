@@ -110,6 +110,16 @@ int ngsq_bam_shard_begin(ngsq_bam *bam, ngsq_ctx *ctx, uint32_t shard, uint32_t 
 /* after ngsq_bam_next_batch_device has returned 0 records */
 int ngsq_bam_shard_end(ngsq_bam *bam, ngsq_bam_shard_info *out);
 
+/* ---- range ingest: the records of one range of virtual offsets (`ngs view`, ngsq_view.h) --------
+ * A shard whose two ends the caller knows, from an index: arms the device ingest to hand out, through
+ * ngsq_bam_next_batch_device, the records from begin_voffset on (a record's first byte; 0: the file's first record) that
+ * start in the blocks up to and including the block of end_voffset -- in front of that block when end_voffset is its first
+ * byte.  Records at or behind end_voffset may thus be handed out: the consumer tells by their record_id.  Built on the sharded
+ * mode's state: the batches count their records from 0, the blocks that complete the last record are read too, and
+ * ngsq_bam_shard_end reports the walk.  May be called again on the same handle for the next range (the previous walk's state
+ * goes; the context's stream is drained first, so that nothing queued still reads its buffers).  Needs a GPU. */
+int ngsq_bam_range_begin(ngsq_bam *bam, ngsq_ctx *ctx, uint64_t begin_voffset, uint64_t end_voffset);
+
 /* What the device ingest of this handle has done so far (measurement and tests: how often the record index had to leave its
  * fast path).  segments: 16 KiB pieces of the inflated stream whose record chain was looked for; walk_one: those whose entry
  * was not among the chain starts the wave had kept (crowded out by bytes that look like records -- auxiliary data can -- or a

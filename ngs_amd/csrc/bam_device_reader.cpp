@@ -1111,20 +1111,8 @@ int find_block_start(FILE *f, uint64_t from, uint64_t file_size, uint64_t *out, 
     }
     auto header_at = [&](size_t p, uint32_t *bsize) {
         if (p + 18 > buf.size()) return false;
-        const uint8_t *c = buf.data() + p;
-        if (c[0] != 31 || c[1] != 139 || c[2] != 8 || !(c[3] & 4)) return false;
-        const uint32_t xlen = bgzf_rd16(c + 10);
-        if (p + 12 + xlen > buf.size()) return false;
-        for (size_t q = p + 12; q + 4 <= p + 12 + xlen;) {
-            const uint32_t slen = bgzf_rd16(buf.data() + q + 2);
-            if (q + 4 + slen > p + 12 + xlen) return false;
-            if (buf[q] == 'B' && buf[q + 1] == 'C' && slen == 2) {
-                *bsize = bgzf_rd16(buf.data() + q + 4) + 1;
-                return *bsize >= 12 + xlen + 8;
-            }
-            q += 4 + slen;
-        }
-        return false;
+        *bsize = bgzf_block_size(buf.data() + p, buf.size() - p);
+        return *bsize != 0;
     };
     for (size_t p = 0; p + 18 <= buf.size() && p < ((size_t)1 << 16) + 18; p++) {
         uint32_t bs = 0;
@@ -1272,6 +1260,66 @@ extern "C" int ngsq_bam_shard_begin(ngsq_bam *b, ngsq_ctx *c, uint32_t shard, ui
     // the workers of one node share its cores: quota less one driving thread and one framing thread per worker
     if (const char *e = getenv("NGSQ_READER_THREADS")) d->reader_threads = atoi(e);
     if (d->reader_threads <= 0) d->reader_threads = std::max(2, (effective_cores() - 2 * (int)n_shards) / (int)n_shards);
+    return start_ingest(b, c, d);
+}
+
+// ---- one range of virtual offsets (include/ngsq_bam.h "range ingest"): a shard whose two ends the caller knows ----------
+extern "C" int ngsq_bam_range_begin(ngsq_bam *b, ngsq_ctx *c, uint64_t begin_voffset, uint64_t end_voffset) {
+    if (!b || !c) return ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "null argument");
+    if (b->host_mode) return ngsq_bam_fail(NGSQ_ERR_STATE, "%s: the reader is in host ingest mode", b->path.c_str());
+    if (begin_voffset && end_voffset < begin_voffset)
+        return ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "%s: the range ends in front of its beginning", b->path.c_str());
+    if (b->dev && (!b->dev->sharded || b->dev->ctx != c)) return ngsq_bam_fail(NGSQ_ERR_STATE, "%s: the reader is already in use", b->path.c_str());
+    BHIP(hipSetDevice(c->device));
+    // ---- the range's byte positions, before anything of the handle changes: a refused call leaves it as it was
+    DeviceIngest *d = nullptr;
+    const int rc = open_ingest(b, c, &d);
+    if (rc) return rc;
+    const uint64_t lo = begin_voffset >> 16, end_coff = end_voffset >> 16;
+    if (lo > d->file_size) {
+        delete d;
+        return ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "%s: virtual offset %llu lies behind the file's end", b->path.c_str(), (unsigned long long)begin_voffset);
+    }
+    // the range's own blocks end behind the block of end_voffset (in front of it when the offset is that block's first byte)
+    uint64_t hi = std::min(end_coff, d->file_size);
+    if ((end_voffset & 0xFFFFu) && end_coff < d->file_size) {
+        uint8_t h[12 + 65536]; // a gzip header with the longest extra field
+        const size_t got = fseeko(d->f, (off_t)end_coff, SEEK_SET) == 0 ? fread(h, 1, sizeof h, d->f) : 0;
+        const uint32_t bs = bgzf_block_size(h, got);
+        if (!bs) {
+            delete d;
+            return ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "%s: virtual offset %llu does not point into a BGZF block", b->path.c_str(), (unsigned long long)end_voffset);
+        }
+        hi = std::min(d->file_size, end_coff + bs);
+    }
+    uint64_t header_bytes = b->header_bytes;
+    if (b->dev) { // the next range: the previous walk's state goes, once nothing queued on the stream reads its buffers any more
+        const hipError_t e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) {
+            delete d;
+            return ngsq_bam_fail(NGSQ_ERR_DEVICE, "hipStreamSynchronize: %s", hipGetErrorString(e));
+        }
+        header_bytes = b->dev->header_bytes0;
+        b->dev_free(b->dev);
+        b->dev = nullptr;
+    }
+    b->dev = d;
+    b->dev_free = free_ingest;
+    b->n_read = 0;
+    b->header_bytes = header_bytes;
+    d->header_bytes0 = header_bytes;
+    d->sharded = true;
+    d->pos_lo = lo; // a block start, by the caller's word: the block chain is followed from there
+    d->pos_hi = std::max(hi, lo);
+    d->pos_end = std::min(d->file_size, d->pos_hi + SHARD_EXTRA);
+    if (begin_voffset) {
+        d->entry_mode = DeviceIngest::ENTRY_KNOWN;
+        d->entry_uoff = begin_voffset & 0xFFFFu;
+    } else {
+        d->entry_mode = DeviceIngest::ENTRY_HEADER; // 0: from the file's first record
+    }
+    if (lo >= d->pos_hi) d->boundary_passed = true; // an empty range
+    if (const char *e = getenv("NGSQ_READER_THREADS")) d->reader_threads = atoi(e);
     return start_ingest(b, c, d);
 }
 

@@ -17,6 +17,25 @@ inline uint32_t bgzf_rd32(const uint8_t *p) {
 }
 inline uint32_t bgzf_rd16(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
 
+// The size of the block whose header starts at h[0, n): BSIZE + 1 of its BC subfield, 0 when the bytes are no whole BGZF
+// header (the gzip magic with FEXTRA, an extra field that lies inside n and holds a BC subfield, a size that has room for
+// the header and the trailer).
+inline uint32_t bgzf_block_size(const uint8_t *h, size_t n) {
+    if (n < 18 || h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4)) return 0;
+    const uint32_t xlen = bgzf_rd16(h + 10);
+    if (12 + (size_t)xlen > n) return 0;
+    for (size_t q = 12; q + 4 <= 12 + (size_t)xlen;) {
+        const uint32_t slen = bgzf_rd16(h + q + 2);
+        if (q + 4 + slen > 12 + (size_t)xlen) return 0;
+        if (h[q] == 'B' && h[q + 1] == 'C' && slen == 2) {
+            const uint32_t bsize = bgzf_rd16(h + q + 4) + 1;
+            return bsize >= 12 + xlen + 8 ? bsize : 0;
+        }
+        q += 4 + slen;
+    }
+    return 0;
+}
+
 // Append every COMPLETE block of c[0..n) to `blocks` (in_off relative to c, out_off running from
 // *out_total) and set *consumed to the bytes they span.  Returns false (with *err) for bytes that
 // are not BGZF.  A trailing incomplete block is left unconsumed, and so is everything from the first

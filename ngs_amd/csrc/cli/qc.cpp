@@ -277,7 +277,7 @@ bool parse_args(int argc, char **argv, Args *out, int *status) {
     }
     if (!saw_qc) {
         usage();
-        bail("this build provides the `qc`, `index`, `convert` and `derive instrument` subcommands only");
+        bail("this build provides the `qc`, `index`, `convert`, `derive instrument` and `view` subcommands only");
     }
     if (pos.size() != 2) {
         usage();

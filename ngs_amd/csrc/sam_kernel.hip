@@ -517,10 +517,18 @@ __device__ uint64_t sam_line(const ngsq_batch &b, const BatchOrigin &o, const Sa
 }
 
 __global__ __launch_bounds__(BT) void k_sam_size(ngsq_batch b, BatchOrigin o, SamRefs R, uint64_t *__restrict__ len,
-                                                 unsigned long long *bad, SamFloats fl) {
+                                                 unsigned long long *bad, SamFloats fl, const uint8_t *__restrict__ keep) {
     const uint64_t i = (uint64_t)blockIdx.x * RECS_PER_BLOCK + (threadIdx.x >> 6);
     const uint64_t n = b.n_records;
     if (i >= n) return; // (a whole wave: i is the wave's)
+    if (keep && !keep[i]) { // a dropped record: no length, no error, no float mark (k_sam_write looks at keep again)
+        if (lane_id() == 0) {
+            len[i] = 0;
+            fl.mark[i] = 0;
+            if (i == n - 1) len[n] = 0;
+        }
+        return;
+    }
     uint32_t err = ~0u;
     bool has_float = false;
     const uint64_t bytes = sam_line<false, false>(b, o, R, i, nullptr, &err, &has_float);
@@ -560,9 +568,10 @@ __global__ void k_sam_total(const uint64_t *__restrict__ off, uint64_t n, const 
 }
 
 __global__ __launch_bounds__(BT) void k_sam_write(ngsq_batch b, BatchOrigin o, SamRefs R, const uint64_t *__restrict__ off,
-                                                  char *__restrict__ text, SamFloats fl) {
+                                                  char *__restrict__ text, SamFloats fl, const uint8_t *__restrict__ keep) {
     const uint64_t i = (uint64_t)blockIdx.x * RECS_PER_BLOCK + (threadIdx.x >> 6);
     if (i >= b.n_records || fl.mark[i]) return; // (a marked record is k_sam_write_floats')
+    if (keep && !keep[i]) return;               // (a dropped record is nobody's)
     uint32_t err = ~0u;
     bool has_float = false;
     (void)sam_line<true, false>(b, o, R, i, text + off[i], &err, &has_float);
@@ -582,13 +591,13 @@ __global__ __launch_bounds__(BT) void k_sam_write_floats(ngsq_batch b, BatchOrig
 } // namespace
 
 hipError_t launch_sam_size(const ngsq_batch &b, const BatchOrigin &o, const SamRefs &refs, uint64_t *len, unsigned long long *bad,
-                           const SamFloats &fl, hipStream_t s) {
+                           const SamFloats &fl, hipStream_t s, const uint8_t *keep) {
     if (!b.n_records) return hipSuccess;
     const uint64_t blocks = (b.n_records + RECS_PER_BLOCK - 1) / RECS_PER_BLOCK;
     if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(fl.count, 0, sizeof(unsigned long long), s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_sam_size, dim3((uint32_t)blocks), dim3(BT), 0, s, b, o, refs, len, bad, fl);
+    hipLaunchKernelGGL(k_sam_size, dim3((uint32_t)blocks), dim3(BT), 0, s, b, o, refs, len, bad, fl, keep);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(k_sam_size_floats, dim3(FLOAT_BLOCKS), dim3(BT), 0, s, b, o, refs, len, bad, fl);
     return hipGetLastError();
@@ -600,11 +609,11 @@ hipError_t launch_sam_total(const uint64_t *off, uint64_t n, const unsigned long
 }
 
 hipError_t launch_sam_write(const ngsq_batch &b, const BatchOrigin &o, const SamRefs &refs, const uint64_t *off, char *text,
-                            const SamFloats &fl, hipStream_t s) {
+                            const SamFloats &fl, hipStream_t s, const uint8_t *keep) {
     if (!b.n_records) return hipSuccess;
     const uint64_t blocks = (b.n_records + RECS_PER_BLOCK - 1) / RECS_PER_BLOCK;
     if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_sam_write, dim3((uint32_t)blocks), dim3(BT), 0, s, b, o, refs, off, text, fl);
+    hipLaunchKernelGGL(k_sam_write, dim3((uint32_t)blocks), dim3(BT), 0, s, b, o, refs, off, text, fl, keep);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_sam_write_floats, dim3(FLOAT_BLOCKS), dim3(BT), 0, s, b, o, refs, off, text, fl);

@@ -40,12 +40,14 @@ struct SamFloats {
 
 // Sizing pass: len[i] = bytes of record i's line (newline included), len[n] = 0; the smallest (index << 8 | code) of a
 // record that cannot be written goes to *bad (atomicMin); fl receives the records that hold a float.  One wave per record.
+// keep (optional, device, [n]; `ngs view`): a record with keep[i] == 0 is dropped -- length 0, no
+// error, no float mark, nothing written by the write pass.  nullptr: every record has its line.
 hipError_t launch_sam_size(const ngsq_batch &b, const BatchOrigin &o, const SamRefs &refs, uint64_t *len, unsigned long long *bad,
-                           const SamFloats &fl, hipStream_t s);
+                           const SamFloats &fl, hipStream_t s, const uint8_t *keep = nullptr);
 // after the exclusive scan of len: host (pinned, device address) receives [off[n], *bad]
 hipError_t launch_sam_total(const uint64_t *off, uint64_t n, const unsigned long long *bad, unsigned long long *host, hipStream_t s);
 // Write pass: record i's line at text + off[i].  One wave per record; SEQ and QUAL a byte per lane.
 hipError_t launch_sam_write(const ngsq_batch &b, const BatchOrigin &o, const SamRefs &refs, const uint64_t *off, char *text,
-                            const SamFloats &fl, hipStream_t s);
+                            const SamFloats &fl, hipStream_t s, const uint8_t *keep = nullptr);
 
 } // namespace ngsq

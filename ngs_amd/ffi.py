@@ -236,6 +236,23 @@ class SamReport(C.Structure):
                 ("total_ms", C.c_double)]
 
 
+# ---- include/ngsq_view.h ----------------------------------------------------------------------
+VIEW_FULL, VIEW_HEADER_ONLY, VIEW_RECORDS_ONLY = 0, 1, 2
+VIEW_MODES = {"full": VIEW_FULL, "header-only": VIEW_HEADER_ONLY, "records-only": VIEW_RECORDS_ONLY}
+VIEW_END_MAX = 1 << 29
+
+
+class ViewChunk(C.Structure):
+    _fields_ = [("begin", C.c_uint64), ("end", C.c_uint64)]
+
+
+class ViewReport(C.Structure):
+    _fields_ = [("records_scanned", C.c_uint64), ("records_written", C.c_uint64), ("header_bytes", C.c_uint64),
+                ("text_bytes", C.c_uint64), ("chunks", C.c_uint64), ("ranges", C.c_uint64), ("batches", C.c_uint64),
+                ("scan_ms", C.c_double), ("select_ms", C.c_double), ("format_ms", C.c_double), ("copy_ms", C.c_double),
+                ("write_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 # ---- include/ngsq_derive.h --------------------------------------------------------------------
 DERIVE_INSTRUMENTS, DERIVE_FLOWCELLS = 0, 1
 
@@ -389,10 +406,15 @@ PROTOTYPES = {
     "ngsq_bam_device_stats": (C.c_int, [C.c_void_p, C.POINTER(IngestStats)]),
     "ngsq_bam_shard_begin": (C.c_int, [C.c_void_p, ctx_p, C.c_uint32, C.c_uint32, C.c_uint64]),
     "ngsq_bam_shard_end": (C.c_int, [C.c_void_p, C.POINTER(ShardInfo)]),
+    "ngsq_bam_range_begin": (C.c_int, [C.c_void_p, ctx_p, C.c_uint64, C.c_uint64]),
     # include/ngsq_index.h
     "ngsq_bam_build_index": (C.c_int, [C.c_void_p, ctx_p, C.c_char_p, C.POINTER(IndexReport)]),
     # include/ngsq_sam.h
     "ngsq_bam_write_sam": (C.c_int, [C.c_void_p, ctx_p, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(SamReport)]),
+    # include/ngsq_view.h
+    "ngsq_bam_query_chunks": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, u32p, u64p, u64p, C.POINTER(ViewChunk), C.c_uint64, u64p]),
+    "ngsq_bam_view": (C.c_int, [C.c_void_p, ctx_p, C.c_int, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint64, C.c_uint64,
+                                C.POINTER(ViewReport)]),
     # include/ngsq_derive.h
     "ngsq_bam_derive_instrument": (C.c_int, [C.c_void_p, ctx_p, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p),
                                              C.POINTER(DeriveReport)]),

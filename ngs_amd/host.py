@@ -561,6 +561,58 @@ def bam_to_sam(path: str, out_path: str, device: int = 0, max_records: int = 0, 
             os.close(fd)
 
 
+def bam_query_chunks(path: str, query: str, bai_path: Optional[str] = None, lib=None):
+    """The region and the merged chunks of a `ngs view` query (include/ngsq_view.h): (ref_id, start, end, [(begin, end), ...])
+    with the 1-based inclusive interval (end = ffi.VIEW_END_MAX for one without an end) and the chunks' virtual offsets, from
+    the index bai_path (default "<path>.bai").  Host only.  NgsqError on an empty query, an unknown sequence, a bad index."""
+    lib = lib or ffi.load_library()
+    bam = C.c_void_p()
+    _check_bam(lib.ngsq_bam_open(path.encode(), 1, C.byref(bam)), lib)
+    try:
+        ref, start, end, n = C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        bai = bai_path.encode() if bai_path else None
+        _check_bam(lib.ngsq_bam_query_chunks(bam, bai, query.encode(), C.byref(ref), C.byref(start), C.byref(end), None, 0, C.byref(n)), lib)
+        chunks = (ffi.ViewChunk * max(n.value, 1))()
+        _check_bam(lib.ngsq_bam_query_chunks(bam, bai, query.encode(), None, None, None, chunks, n.value, C.byref(n)), lib)
+        return ref.value, start.value, end.value, [(chunks[k].begin, chunks[k].end) for k in range(n.value)]
+    finally:
+        lib.ngsq_bam_close(bam)
+
+
+def bam_view(path: str, out_path: str, query: Optional[str] = None, mode: str = "full", device: int = 0, bai_path: Optional[str] = None,
+             batch_records: int = 0, coalesce_gap: int = 0, lib=None) -> Dict[str, float]:
+    """`ngs view <BAM> [QUERY]` in process (include/ngsq_view.h): the view of `path` written to out_path (created or truncated).
+    query None: every record; mode "full" | "header-only" | "records-only" ("header-only" needs no GPU); bai_path: the index of
+    a query (default "<path>.bai"); batch_records: records per ingest batch (0: the library's default); coalesce_gap: merged
+    chunks nearer than this many compressed bytes share a range walk (0: the default, 1: a walk each).  Returns the report;
+    NgsqError on an open failure, a bad query or index, or a selected record without SAM text."""
+    lib = lib or ffi.load_library()
+    m = ffi.VIEW_MODES[mode]
+    q = query.encode() if query is not None else None
+    bai = bai_path.encode() if bai_path else None
+
+    def run(bam, ctx):
+        fd = os.open(out_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o666)
+        try:
+            rep = ffi.ViewReport()
+            _check_bam(lib.ngsq_bam_view(bam, ctx, fd, q, bai, m, batch_records, coalesce_gap, C.byref(rep)), lib)
+            return {k: getattr(rep, k) for k, _ in ffi.ViewReport._fields_}
+        finally:
+            os.close(fd)
+
+    if m == ffi.VIEW_HEADER_ONLY:
+        bam = C.c_void_p()
+        rc = lib.ngsq_bam_open(path.encode(), 1, C.byref(bam))
+        if rc != ffi.OK:
+            raise NgsqError(rc, "opening BAM input file: " + (lib.ngsq_bam_last_error() or b"").decode("utf-8", "replace"))
+        try:
+            return run(bam, None)
+        finally:
+            lib.ngsq_bam_close(bam)
+    with _reader_and_plain_context(lib, path, device, "opening BAM input file: ") as (bam, ctx):
+        return run(bam, ctx)
+
+
 def _c_strings(items: Sequence[bytes]):
     """(char **, uint32_t *, n) for byte strings that may be empty or hold any byte; keep the result while they are in use."""
     bufs = [C.create_string_buffer(bytes(x), len(x) + 1) for x in items]
