@@ -162,7 +162,9 @@ void usage() {
             "      --gpus <N>                  One worker per GPU over BGZF block ranges of the file, one RCCL exchange (additive)\n\n"
             "       ngs [-q|-v] index [--device <N>] <BAM>   Write <BAM>.bai, built on the GPU (BAM only in this build)\n"
             "       ngs [-q|-v] convert [OPTIONS] <FROM> <TO>   Convert BAM to SAM, the text formatted on the GPU (BAM to SAM only in\n"
-            "                                                   this build)\n");
+            "                                                   this build)\n"
+            "       ngs [-q|-v] generate [OPTIONS] <-n <USIZE>|-c <USIZE>> <READ_ONES_FILE> <READ_TWOS_FILE> <REFERENCE_PROVIDERS>...\n"
+            "                                                   Paired FASTQ reads sampled from reference FASTAs, drawn and written on the GPU\n");
 }
 
 #define CHECK(ctx, expr)                                                                                   \
@@ -277,7 +279,7 @@ bool parse_args(int argc, char **argv, Args *out, int *status) {
     }
     if (!saw_qc) {
         usage();
-        bail("this build provides the `qc`, `index`, `convert`, `derive instrument` and `view` subcommands only");
+        bail("this build provides the `qc`, `index`, `convert`, `derive instrument`, `view` and `generate` subcommands only");
     }
     if (pos.size() != 2) {
         usage();

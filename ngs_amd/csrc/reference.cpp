@@ -29,6 +29,7 @@
 #include "context.h"
 #include "mem_pool.h"
 #include "reference_kernels.h"
+#include "reference_load.h"
 
 namespace {
 
@@ -583,6 +584,160 @@ int load_main(Loader *L) {
 }
 
 } // namespace
+
+// ---------------------------------------------------------------------------------------------------------------------
+// every record as letters (`ngs generate`): reference_load.h
+// ---------------------------------------------------------------------------------------------------------------------
+namespace ngsq {
+
+int fasta_record_bases(ngsq_fasta *f, std::vector<uint64_t> *bases, std::string *err) {
+    wait_index(f);
+    if (!f->index_err.empty()) {
+        *err = f->index_err;
+        return NGSQ_ERR_INVALID_ARGUMENT;
+    }
+    const size_t n = f->recs.size();
+    bases->assign(n, 0);
+    std::atomic<size_t> next{0};
+    auto work = [&] {
+        for (size_t i = next.fetch_add(1); i < n; i = next.fetch_add(1)) {
+            const uint64_t lo = f->recs[i].text_begin, hi = f->recs[i].text_end;
+            // dropped, as load_own of reference_kernels.hip drops them: every '\n', and a '\r' in front of one or of the text's end
+            uint64_t dropped = 0;
+            for (uint64_t p = lo; p < hi;) {
+                const uint8_t *q = static_cast<const uint8_t *>(memchr(f->map + p, '\n', hi - p));
+                if (!q) break;
+                const uint64_t at = (uint64_t)(q - f->map);
+                dropped += 1 + (at > lo && f->map[at - 1] == '\r');
+                p = at + 1;
+            }
+            if (hi > lo && f->map[hi - 1] == '\r') dropped++;
+            (*bases)[i] = hi - lo - dropped;
+        }
+    };
+    const int nt = (int)std::max<size_t>(1, std::min<size_t>((size_t)f->n_threads, n));
+    std::vector<std::thread> th;
+    for (int t = 1; t < nt; t++) th.emplace_back(work);
+    work();
+    for (auto &x : th) x.join();
+    return NGSQ_OK;
+}
+
+FastaLetters::~FastaLetters() { pool_device_free(d, got); }
+
+int fasta_load_letters(ngsq_fasta *f, int device, const LaunchInfo &li, FastaLetters *out, std::string *err) {
+    auto fail = [&](int code, const std::string &why) {
+        *err = why;
+        return code;
+    };
+    wait_index(f);
+    if (!f->index_err.empty()) return fail(NGSQ_ERR_INVALID_ARGUMENT, f->index_err);
+    const size_t nseq = f->recs.size();
+    out->off.assign(nseq, 0);
+    out->len.assign(nseq, 0);
+    if (!nseq) return NGSQ_OK;
+    uint64_t total = 0, n_tiles = 0;
+    std::vector<FastaSeqDev> seqs(nseq);
+    std::vector<uint64_t> tile_first(nseq + 1, 0);
+    for (size_t k = 0; k < nseq; k++) {
+        const FaRecord &rec = f->recs[k];
+        const uint64_t len = rec.text_end - rec.text_begin;
+        if (len >= (1ull << 32))
+            return fail(NGSQ_ERR_LIMIT, "sequence " + rec.name + ": " + std::to_string(len) + " bytes of FASTA text; the loader takes records below 4 GiB");
+        seqs[k] = FastaSeqDev{total, len};
+        out->off[k] = total;
+        tile_first[k] = n_tiles;
+        n_tiles += (len + FASTA_TILE - 1) / FASTA_TILE;
+        total += (len + 255) & ~255ull;
+        out->text_bytes += len;
+    }
+    tile_first[nseq] = n_tiles;
+    hipStream_t stream = nullptr;
+    uint8_t *d_text = nullptr;
+    size_t text_got = 0;
+    void *d_small = nullptr; // seqs | tile_first | seq_len
+    uint32_t *d_counts = nullptr;
+    uint64_t *d_tile_base = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    const size_t off_tf = nseq * sizeof(FastaSeqDev), off_len = off_tf + (nseq + 1) * 8, small_bytes = off_len + nseq * 8;
+    Uploader up;
+    auto cleanup = [&]() {
+        if (stream) (void)hipStreamSynchronize(stream);
+        pool_device_free(d_text, text_got);
+        (void)hipFree(d_small);
+        (void)hipFree(d_counts);
+        (void)hipFree(d_tile_base);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        for (int s = 0; s < N_SLOTS; s++) {
+            if (up.slot[s]) pool_pinned_free(up.slot[s], up.slot_bytes[s]);
+            if (up.ev[s]) pool_event_put(up.ev[s]);
+        }
+        if (stream) pool_stream_put(false, stream);
+    };
+#define GTRY(expr)                                                                                  \
+    do {                                                                                            \
+        hipError_t e_ = (expr);                                                                     \
+        if (e_ != hipSuccess) {                                                                     \
+            cleanup();                                                                              \
+            return fail(NGSQ_ERR_DEVICE, std::string(#expr " failed: ") + hipGetErrorString(e_));   \
+        }                                                                                           \
+    } while (0)
+    GTRY(hipSetDevice(device));
+    GTRY(pool_stream_get(false, &stream));
+    GTRY(pool_device_alloc((void **)&d_text, total + 256, &text_got));
+    GTRY(pool_device_alloc((void **)&out->d, total + 256, &out->got));
+    GTRY(hipMalloc(&d_small, small_bytes));
+    GTRY(hipMalloc((void **)&d_counts, (n_tiles + 1) * 4));
+    GTRY(hipMalloc((void **)&d_tile_base, (n_tiles + 1) * 8));
+    uint8_t *sm = static_cast<uint8_t *>(d_small);
+    GTRY(hipMemsetAsync(sm + off_len, 0, small_bytes - off_len, stream));
+    GTRY(hipMemcpyAsync(sm, seqs.data(), nseq * sizeof(FastaSeqDev), hipMemcpyHostToDevice, stream));
+    GTRY(hipMemcpyAsync(sm + off_tf, tile_first.data(), (nseq + 1) * 8, hipMemcpyHostToDevice, stream));
+    // ---- the text: file -> pinned slots -> device, a few threads (the ring of ngsq_reference_load)
+    const double t_read = now_s();
+    up.fd = f->fd;
+    up.d_text = d_text;
+    up.stream = stream;
+    up.device = device;
+    for (size_t k = 0; k < nseq; k++)
+        for (uint64_t o = 0; o < seqs[k].text_len; o += SLOT)
+            up.pieces.push_back(Piece{f->recs[k].text_begin + o, seqs[k].text_off + o, std::min<uint64_t>(SLOT, seqs[k].text_len - o)});
+    for (int s = 0; s < N_SLOTS; s++) {
+        up.issued[s] = (int64_t)s - N_SLOTS;
+        if ((size_t)s < up.pieces.size()) {
+            GTRY(pool_pinned_alloc(&up.slot[s], SLOT, &up.slot_bytes[s]));
+            GTRY(pool_event_get(&up.ev[s]));
+        }
+    }
+    {
+        const int nt = (int)std::min<size_t>((size_t)f->n_threads, up.pieces.size());
+        std::vector<std::thread> th;
+        for (int t = 0; t < nt; t++) th.emplace_back([&up] { up.work(); });
+        for (auto &x : th) x.join();
+    }
+    if (up.bad) {
+        cleanup();
+        return fail(NGSQ_ERR_DEVICE, up.err);
+    }
+    out->read_s = now_s() - t_read;
+    // ---- text -> letters
+    GTRY(hipEventCreate(&e0));
+    GTRY(hipEventCreate(&e1));
+    GTRY(hipEventRecord(e0, stream));
+    GTRY(launch_fasta_convert(li, d_text, reinterpret_cast<FastaSeqDev *>(sm), (uint32_t)nseq, reinterpret_cast<uint64_t *>(sm + off_tf), n_tiles, d_counts,
+                              d_tile_base, reinterpret_cast<unsigned long long *>(sm + off_len), out->d, nullptr, nullptr, 0, stream, true));
+    GTRY(hipEventRecord(e1, stream));
+    GTRY(hipMemcpyAsync(out->len.data(), sm + off_len, nseq * 8, hipMemcpyDeviceToHost, stream));
+    GTRY(hipStreamSynchronize(stream));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) out->device_s = ms * 1e-3;
+    cleanup();
+    return NGSQ_OK;
+#undef GTRY
+}
+
+} // namespace ngsq
 
 namespace ngsq {
 

@@ -25,8 +25,10 @@ int fasta_base_code(uint8_t byte);
 // tile_first[s] = index of the record's first tile (n_seq + 1 entries, tiles of FASTA_TILE bytes); counts [n_tiles] and
 // tile_base [n_tiles] are scratch.  Bytes that are no base letter: *n_bad counts them, bad_list[k] = record << 40 | 1-based
 // position for the first bad_cap of them (their code slot holds N).  The text buffer must be readable 64 bytes past its end.
+// raw: codes[...] receives the bytes themselves instead (line terminators dropped, every other byte kept); n_bad and bad_list
+// are not touched.
 hipError_t launch_fasta_convert(const LaunchInfo &li, const uint8_t *text, const FastaSeqDev *seqs, uint32_t n_seq, const uint64_t *tile_first,
                                 uint64_t n_tiles, uint32_t *counts, uint64_t *tile_base, unsigned long long *seq_len, uint8_t *codes,
-                                unsigned long long *n_bad, unsigned long long *bad_list, uint32_t bad_cap, hipStream_t s);
+                                unsigned long long *n_bad, unsigned long long *bad_list, uint32_t bad_cap, hipStream_t s, bool raw = false);
 
 } // namespace ngsq

@@ -6,7 +6,8 @@
 //   k_fasta_count   bases per 4 KiB tile of text (a byte is dropped iff it is '\n', or a '\r' in front of a '\n' / of the end)
 //   k_fasta_scan    per record: exclusive prefix of its tiles' counts -> where each tile's bases go; the record's length
 //   k_fasta_emit    the bases of every tile as codes, compacted through LDS and stored with coalesced dwords; bytes that are
-//                   no base letter are listed (record, 1-based position) -- only a read that covers one fails
+//                   no base letter are listed (record, 1-based position) -- only a read that covers one fails.  Its second
+//                   mode keeps the letters themselves (`ngs generate` needs their case): same tiles, same offsets
 // All HBM-bound byte work: 3.1 GB of text in, 3.1 GB of codes out, a few milliseconds per genome.
 #include <hip/hip_runtime.h>
 
@@ -137,6 +138,8 @@ __global__ __launch_bounds__(1024) void k_fasta_scan(const uint32_t *__restrict_
     if (t == 0) seq_len[s] = s_carry;
 }
 
+// RAW (`ngs generate`): every kept byte as it is -- case and all -- and no list of bad bytes
+template <bool RAW>
 __global__ __launch_bounds__(THREADS) void k_fasta_emit(const uint8_t *__restrict__ text, const FastaSeqDev *__restrict__ seqs, uint32_t n_seq,
                                                         const uint64_t *__restrict__ tile_first, uint64_t n_tiles,
                                                         const uint64_t *__restrict__ tile_base, uint8_t *__restrict__ codes,
@@ -166,8 +169,8 @@ __global__ __launch_bounds__(THREADS) void k_fasta_emit(const uint8_t *__restric
         for (uint32_t j = 0; j < 16; j++) {
             if (!((o.keep >> j) & 1u)) continue;
             const uint32_t ch = (ww[j >> 2] >> (8u * (j & 3u))) & 0xFFu;
-            uint32_t code = base_code_of(ch);
-            if (code > 15u) { // no base letter: the position is remembered (1-based), the slot holds N
+            uint32_t code = RAW ? ch : base_code_of(ch);
+            if (!RAW && code > 15u) { // no base letter: the position is remembered (1-based), the slot holds N
                 const unsigned long long k = atomicAdd(n_bad, 1ull);
                 if (k < bad_cap) bad_list[k] = (unsigned long long)s << 40 | (first + at + 1);
                 code = 15u;
@@ -200,12 +203,13 @@ int fasta_base_code(uint8_t byte) {
 
 hipError_t launch_fasta_convert(const LaunchInfo &li, const uint8_t *text, const FastaSeqDev *seqs, uint32_t n_seq, const uint64_t *tile_first,
                                 uint64_t n_tiles, uint32_t *counts, uint64_t *tile_base, unsigned long long *seq_len, uint8_t *codes,
-                                unsigned long long *n_bad, unsigned long long *bad_list, uint32_t bad_cap, hipStream_t s) {
+                                unsigned long long *n_bad, unsigned long long *bad_list, uint32_t bad_cap, hipStream_t s, bool raw) {
     if (!n_seq || !n_tiles) return hipSuccess;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)li.n_cu * 16);
     hipLaunchKernelGGL(k_fasta_count, dim3(grid), dim3(THREADS), 0, s, text, seqs, n_seq, tile_first, n_tiles, counts);
     hipLaunchKernelGGL(k_fasta_scan, dim3(n_seq), dim3(1024), 0, s, counts, tile_first, n_seq, tile_base, seq_len);
-    hipLaunchKernelGGL(k_fasta_emit, dim3(grid), dim3(THREADS), 0, s, text, seqs, n_seq, tile_first, n_tiles, tile_base, codes, n_bad, bad_list, bad_cap);
+    if (raw) hipLaunchKernelGGL(k_fasta_emit<true>, dim3(grid), dim3(THREADS), 0, s, text, seqs, n_seq, tile_first, n_tiles, tile_base, codes, n_bad, bad_list, bad_cap);
+    else hipLaunchKernelGGL(k_fasta_emit<false>, dim3(grid), dim3(THREADS), 0, s, text, seqs, n_seq, tile_first, n_tiles, tile_base, codes, n_bad, bad_list, bad_cap);
     return hipGetLastError();
 }
 

@@ -253,6 +253,22 @@ class ViewReport(C.Structure):
                 ("write_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+# ---- include/ngsq_generate.h ------------------------------------------------------------------
+GENERATE_MAX_TABLE = 1 << 20
+GENERATE_MAX_ATTEMPTS = 1024
+
+
+class GenerateProvider(C.Structure):
+    _fields_ = [("path", C.c_char_p), ("error_freq", C.c_uint64), ("mu", C.c_double), ("sigma", C.c_double),
+                ("read_length", C.c_uint64), ("weight", C.c_uint64)]
+
+
+class GenerateReport(C.Structure):
+    _fields_ = [("pairs", C.c_uint64), ("rejected_start", C.c_uint64), ("rejected_end", C.c_uint64), ("rejected_base", C.c_uint64),
+                ("text_bytes_one", C.c_uint64), ("text_bytes_two", C.c_uint64), ("batches", C.c_uint64), ("draw_ms", C.c_double),
+                ("format_ms", C.c_double), ("copy_ms", C.c_double), ("write_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 # ---- include/ngsq_derive.h --------------------------------------------------------------------
 DERIVE_INSTRUMENTS, DERIVE_FLOWCELLS = 0, 1
 
@@ -415,6 +431,22 @@ PROTOTYPES = {
     "ngsq_bam_query_chunks": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, u32p, u64p, u64p, C.POINTER(ViewChunk), C.c_uint64, u64p]),
     "ngsq_bam_view": (C.c_int, [C.c_void_p, ctx_p, C.c_int, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint64, C.c_uint64,
                                 C.POINTER(ViewReport)]),
+    # include/ngsq_generate.h
+    "ngsq_generate_last_error": (C.c_char_p, []),
+    "ngsq_generate_parse_provider": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(GenerateProvider), C.c_char_p, C.c_size_t]),
+    "ngsq_generate_check_provider": (C.c_int, [C.POINTER(GenerateProvider), C.c_char_p, C.c_char_p, C.c_size_t]),
+    "ngsq_generate_inner_table": (C.c_int, [C.c_double, C.c_double, C.POINTER(C.c_int64), u64p, C.c_uint64, u64p, C.c_char_p, C.c_size_t]),
+    "ngsq_generate_draw": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "ngsq_generate_open": (C.c_int, [C.POINTER(GenerateProvider), C.c_uint32, C.POINTER(C.c_void_p)]),
+    "ngsq_generate_close": (None, [C.c_void_p]),
+    "ngsq_generate_reads_for_coverage": (C.c_uint64, [C.c_void_p, C.c_uint64]),
+    "ngsq_generate_n_sequences": (C.c_uint32, [C.c_void_p, C.c_uint32]),
+    "ngsq_generate_sequence_name": (C.c_char_p, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "ngsq_generate_sequence_length": (C.c_uint64, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "ngsq_generate_load": (C.c_int, [C.c_void_p, ctx_p]),
+    "ngsq_generate_write": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(GenerateReport)]),
+    "ngsq_gzip_pipe_open": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
+    "ngsq_gzip_pipe_close": (C.c_int, [C.c_void_p]),
     # include/ngsq_derive.h
     "ngsq_bam_derive_instrument": (C.c_int, [C.c_void_p, ctx_p, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p),
                                              C.POINTER(DeriveReport)]),

@@ -668,3 +668,107 @@ def derive_instrument(path: str, device: int = 0, max_records: int = 0, batch_re
             lib.ngsq_derive_names_free(names)
         doc = json.loads(derive_predict(sets[0], sets[1], lib))
         return sets[0], sets[1], doc, {k: getattr(rep, k) for k, _ in ffi.DeriveReport._fields_}
+
+
+def _check_generate(rc: int, lib):
+    if rc != ffi.OK:
+        raise NgsqError(rc, (lib.ngsq_generate_last_error() or b"").decode("utf-8", "replace"))
+
+
+def generate_inner_table(mu: float, sigma: float, lib=None):
+    """(lower, table) of the inner distance of N(mu, sigma) (include/ngsq_generate.h: ngsq_generate_inner_table): the integers
+    lower .. lower + len(table) - 1 and their cumulative 64-bit thresholds.  Host only.  NgsqError on a refused distribution."""
+    lib = lib or ffi.load_library()
+    lower, n = C.c_int64(), C.c_uint64()
+    err = C.create_string_buffer(512)
+    rc = lib.ngsq_generate_inner_table(mu, sigma, C.byref(lower), None, 0, C.byref(n), err, len(err))
+    if rc != ffi.OK:
+        raise NgsqError(rc, err.value.decode("utf-8", "replace"))
+    table = np.zeros(n.value, dtype=np.uint64)
+    lib.ngsq_generate_inner_table(mu, sigma, C.byref(lower), table.ctypes.data_as(ffi.u64p), n.value, C.byref(n), err, len(err))
+    return lower.value, table
+
+
+def parse_provider(text: str, lib=None):
+    """A provider string PATH:ERROR_FREQ:MU:SIGMA:READ_LENGTH:WEIGHT as (path, error_freq, mu, sigma, read_length, weight)
+    (include/ngsq_generate.h: ngsq_generate_parse_provider).  NgsqError carries the reference's message."""
+    lib = lib or ffi.load_library()
+    raw = text.encode()
+    path, err, p = C.create_string_buffer(len(raw) + 1), C.create_string_buffer(1024), ffi.GenerateProvider()
+    rc = lib.ngsq_generate_parse_provider(raw, path, len(path), C.byref(p), err, len(err))
+    if rc != ffi.OK:
+        raise NgsqError(rc, err.value.decode("utf-8", "replace"))
+    return path.value.decode(), p.error_freq, p.mu, p.sigma, p.read_length, p.weight
+
+
+class Generator:
+    """`ngs generate` in process (include/ngsq_generate.h).  providers: (path, error_freq, mu, sigma, read_length, weight) each.
+    Opening is host only and raises NgsqError on every up-front refusal; write() brings the FASTAs to GPU `device` the first
+    time and writes pairs [first_pair, first_pair + n_pairs) to the two paths (created or truncated; append=True adds to them)."""
+
+    def __init__(self, providers, device: int = 0, lib=None):
+        self.lib = lib or ffi.load_library()
+        self.device = device
+        self._g, self._ctx = C.c_void_p(), None
+        self._paths = [str(p[0]).encode() for p in providers]
+        arr = (ffi.GenerateProvider * max(len(providers), 1))()
+        for k, (_, ef, mu, sigma, rl, wt) in enumerate(providers):
+            arr[k].path, arr[k].error_freq, arr[k].mu, arr[k].sigma, arr[k].read_length, arr[k].weight = self._paths[k], ef, mu, sigma, rl, wt
+        _check_generate(self.lib.ngsq_generate_open(arr, len(providers), C.byref(self._g)), self.lib)
+        self.n_providers = len(providers)
+
+    def sequences(self, p: int = 0):
+        """[(name, bases)] of provider p, in file order."""
+        return [(self.lib.ngsq_generate_sequence_name(self._g, p, s), self.lib.ngsq_generate_sequence_length(self._g, p, s))
+                for s in range(self.lib.ngsq_generate_n_sequences(self._g, p))]
+
+    def reads_for_coverage(self, coverage: int) -> int:
+        return self.lib.ngsq_generate_reads_for_coverage(self._g, coverage)
+
+    def load(self):
+        if self._ctx is None:
+            cfg = ffi.Config()
+            cfg.struct_size = C.sizeof(ffi.Config)
+            cfg.facets, cfg.device, cfg.n_refs = 0, self.device, 0
+            ctx = ffi.ctx_p()
+            _check(self.lib.ngsq_create(C.byref(cfg), C.byref(ctx)), None, self.lib)
+            self._ctx = ctx
+            _check_generate(self.lib.ngsq_generate_load(self._g, ctx), self.lib)
+
+    def write_fds(self, fd_one: int, fd_two: int, seed: int, n_pairs: int, first_pair: int = 0, batch_pairs: int = 0) -> Dict[str, float]:
+        self.load()
+        rep = ffi.GenerateReport()
+        _check_generate(self.lib.ngsq_generate_write(self._g, fd_one, fd_two, seed, first_pair, n_pairs, batch_pairs, C.byref(rep)), self.lib)
+        return {k: getattr(rep, k) for k, _ in ffi.GenerateReport._fields_}
+
+    def write(self, path_one: str, path_two: str, seed: int, n_pairs: int, first_pair: int = 0, batch_pairs: int = 0, append: bool = False):
+        flags = os.O_WRONLY | os.O_CREAT | (os.O_APPEND if append else os.O_TRUNC)
+        fd1 = os.open(path_one, flags, 0o666)
+        try:
+            fd2 = os.open(path_two, flags, 0o666)
+            try:
+                return self.write_fds(fd1, fd2, seed, n_pairs, first_pair, batch_pairs)
+            finally:
+                os.close(fd2)
+        finally:
+            os.close(fd1)
+
+    def close(self):
+        if self._g:
+            self.lib.ngsq_generate_close(self._g)
+            self._g = C.c_void_p()
+        if self._ctx is not None:
+            self.lib.ngsq_destroy(self._ctx)
+            self._ctx = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def generate(providers, path_one: str, path_two: str, seed: int, n_pairs: int, first_pair: int = 0, batch_pairs: int = 0, device: int = 0, lib=None):
+    """One call of `ngs generate` in process: the report of Generator.write."""
+    with Generator(providers, device=device, lib=lib) as g:
+        return g.write(path_one, path_two, seed, n_pairs, first_pair, batch_pairs)
