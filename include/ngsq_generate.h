@@ -102,6 +102,27 @@ typedef struct ngsq_generate_report {
 int ngsq_generate_write(ngsq_generate *g, int fd_one, int fd_two, uint64_t seed, uint64_t first_pair, uint64_t n_pairs,
                         uint64_t batch_pairs, ngsq_generate_report *out);
 
+/* ---- BGZF written on the device ------------------------------------------------------------------------- */
+
+#define NGSQ_GENERATE_PLAIN_ONE 1u /* flags: fd_one receives plain text, as from ngsq_generate_write */
+#define NGSQ_GENERATE_PLAIN_TWO 2u /* ... fd_two */
+
+typedef struct ngsq_generate_bgzf_report {
+    ngsq_generate_report text;     /* what ngsq_generate_write reports; copy_ms and write_ms are of the bytes that crossed */
+    uint64_t compressed_bytes_one; /* bytes of BGZF written to fd_one, the EOF block among them (0: plain) */
+    uint64_t compressed_bytes_two;
+    uint64_t blocks, stored_blocks; /* BGZF blocks of both files without the EOF blocks; those left stored */
+    double deflate_ms;              /* GPU time of the encoder, its CRC and its pack */
+} ngsq_generate_bgzf_report;
+
+/* ngsq_generate_write with each batch's text compressed on the device (ngsq_bgzf.h) behind the kernel that writes it: only
+ * BGZF blocks cross to the host, and each descriptor receives the 28-byte EOF block after its last batch.  n_pairs == 0
+ * writes the EOF block alone (and needs no ngsq_generate_load).  The DECOMPRESSED bytes depend on (providers, seed, pair
+ * index) alone, as ngsq_generate_write's do; the compressed bytes also depend on batch_pairs, because every batch ends its
+ * last block.  flags: 0, or NGSQ_GENERATE_PLAIN_* for a file that is to stay plain text.  Errors as ngsq_generate_write. */
+int ngsq_generate_write_bgzf(ngsq_generate *g, int fd_one, int fd_two, uint64_t seed, uint64_t first_pair, uint64_t n_pairs,
+                             uint64_t batch_pairs, uint32_t flags, ngsq_generate_bgzf_report *out);
+
 /* ---- gzipped FASTQ ------------------------------------------------------------------------------------------------------------ */
 
 /* A pipe whose read end is compressed (zlib level 6, one gzip member per piece of at most 1 MiB) by n_threads threads

@@ -12,13 +12,13 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libngsq.so")
-SOURCES = ["kernels.hip", "qual_kernel.hip", "fields_kernel.hip", "cov_scan.hip", "cov_stream.hip", "synth.hip", "bgzf_inflate.hip",
+SOURCES = ["kernels.hip", "qual_kernel.hip", "fields_kernel.hip", "cov_scan.hip", "cov_stream.hip", "synth.hip", "bgzf_inflate.hip", "bgzf_deflate.hip", "bgzf_deflate.cpp",
            "bam_device.hip", "features_kernel.hip", "edits_kernel.hip", "exchange_kernels.hip", "comm.cpp", "exchange.cpp", "mem_pool.cpp", "context.cpp", "stager.cpp", "results.cpp", "bam_reader.cpp", "bam_device_reader.cpp", "synth_bam.cpp",
            "reference.cpp", "reference_kernels.hip", "bai_kernel.hip", "bai.cpp",
            "sam_kernel.hip", "sam.cpp", "derive_kernel.hip", "derive.cpp",
            "view_kernel.hip", "view_query.cpp", "view.cpp",
            "generate_kernel.hip", "generate_args.cpp", "generate_gzip.cpp", "generate.cpp"]
-HEADERS = ["kernels.h", "context.h", "comm.h", "mem_pool.h", "bam_reader.h", "ingest_consumer.h", "ingest_kernels.h", "bgzf.h", "reference_kernels.h", "../../include/ngsq.h",
+HEADERS = ["kernels.h", "context.h", "comm.h", "mem_pool.h", "bam_reader.h", "ingest_consumer.h", "ingest_kernels.h", "bgzf.h", "bgzf_crc.h", "deflate_kernels.h", "../../include/ngsq_bgzf.h", "reference_kernels.h", "../../include/ngsq.h",
            "../../include/ngsq_reference.h", "../../include/ngsq_comm.h",
            "../../include/ngsq_shared.h", "../../include/ngsq_synth.h", "../../include/ngsq_bam.h", "../../include/ngsq_stage.h",
            "bai_kernels.h", "../../include/ngsq_index.h", "sam_kernels.h", "../../include/ngsq_sam.h",
@@ -49,7 +49,7 @@ CLI_DIR = os.path.join(CSRC, "cli")
 CLI_SOURCES = [os.path.join(CLI_DIR, f) for f in ("ngs_main.cpp", "qc.cpp", "index.cpp", "convert.cpp", "derive.cpp", "view.cpp", "generate.cpp")]  # one file per command
 CLI_HEADERS = sorted(os.path.join(CLI_DIR, f) for f in os.listdir(CLI_DIR) if f.endswith(".h"))
 CLI_PUBLIC_HEADERS = [os.path.join(HERE, "..", "include", f) for f in (
-    "ngsq.h", "ngsq_bam.h", "ngsq_comm.h", "ngsq_derive.h", "ngsq_generate.h", "ngsq_index.h", "ngsq_reference.h", "ngsq_sam.h", "ngsq_stage.h", "ngsq_view.h")]
+    "ngsq.h", "ngsq_bam.h", "ngsq_bgzf.h", "ngsq_comm.h", "ngsq_derive.h", "ngsq_generate.h", "ngsq_index.h", "ngsq_reference.h", "ngsq_sam.h", "ngsq_stage.h", "ngsq_view.h")]
 CLI_OUT = os.path.join(HERE, "ngs")
 
 

@@ -16,6 +16,7 @@ struct GenerateArgs {
     bool has_n = false, has_c = false, has_seed = false;
     unsigned long long n = 0, coverage = 0, seed = 0, batch_pairs = 0;
     int device = 0;
+    bool gzip_device = false; // --gzip device: .gz outputs are BGZF written on the GPU
 };
 
 const char *const USAGE = "Usage: ngs generate [OPTIONS] <--num-records <USIZE>|--coverage <USIZE>> <READ_ONES_FILE> <READ_TWOS_FILE> <REFERENCE_PROVIDERS>...";
@@ -66,7 +67,11 @@ bool parse_args(int argc, char **argv, int at, GenerateArgs *a) {
                     "      --device <N>\n"
                     "          GPU the pairs are drawn and written on (additive, this build) [default: 0]\n"
                     "      --batch-pairs <N>\n"
-                    "          Pairs per launch; the output does not depend on it (additive, this build)\n\n"
+                    "          Pairs per launch; the output does not depend on it (additive, this build)\n"
+                    "      --gzip <WHERE>\n"
+                    "          Where gzipped outputs are compressed (additive, this build): host threads behind a pipe, or the GPU,\n"
+                    "          which writes BGZF and sends only compressed bytes to the host; plain outputs are not affected\n"
+                    "          [default: host] [possible values: host, device]\n\n"
                     "Outputs are FASTQ (.fastq, .fq) or gzipped FASTQ (.fastq.gz, .fq.gz).\n",
                     USAGE);
             return false;
@@ -83,6 +88,11 @@ bool parse_args(int argc, char **argv, int at, GenerateArgs *a) {
             a->has_seed = true;
         } else if (s == "--batch-pairs") {
             a->batch_pairs = usize_value(val("--batch-pairs <N>"), "--batch-pairs <N>");
+        } else if (s == "--gzip") {
+            const std::string v = val("--gzip <WHERE>");
+            if (v == "host") a->gzip_device = false;
+            else if (v == "device") a->gzip_device = true;
+            else bail("invalid value '" + v + "' for '--gzip <WHERE>' [possible values: host, device]");
         } else if (s == "--device") {
             a->device = atoi(val("--device <N>").c_str());
         } else if (!s.empty() && s[0] == '-' && s != "-") bail("unexpected argument '" + s + "' found");
@@ -168,6 +178,8 @@ int generate_main(int argc, char **argv, int at) {
     }
     // (2) the device, the FASTAs' way to it, the pairs
     ngsq_generate_report rep{};
+    ngsq_generate_bgzf_report zrep{};
+    const bool on_device = a.gzip_device && (o[0].gzip || o[1].gzip);
     std::string msg;
     ngsq_ctx *ctx = nullptr;
     if (total) {
@@ -178,9 +190,14 @@ int generate_main(int argc, char **argv, int at) {
         if (ngsq_create(&cfg, &ctx) != NGSQ_OK) msg = ngsq_last_global_error();
         else if (ngsq_generate_load(g, ctx) != NGSQ_OK) msg = ngsq_generate_last_error();
     }
-    for (int k = 0; k < 2 && msg.empty(); k++)
+    for (int k = 0; k < 2 && msg.empty() && !on_device; k++)
         if (o[k].gzip && ngsq_gzip_pipe_open(o[k].fd, 8, &o[k].gz, &o[k].write_fd) != NGSQ_OK) msg = std::string(octx[k]) + o[k].path + ": could not start the compressor";
-    if (msg.empty() && total && ngsq_generate_write(g, o[0].write_fd, o[1].write_fd, a.seed, 0, total, a.batch_pairs, &rep) != NGSQ_OK)
+    if (msg.empty() && on_device) {
+        // (also without a pair: a compressed output is the EOF block then, where the host path writes one empty member)
+        const uint32_t plain = (o[0].gzip ? 0u : NGSQ_GENERATE_PLAIN_ONE) | (o[1].gzip ? 0u : NGSQ_GENERATE_PLAIN_TWO);
+        if (ngsq_generate_write_bgzf(g, o[0].write_fd, o[1].write_fd, a.seed, 0, total, a.batch_pairs, plain, &zrep) != NGSQ_OK) msg = ngsq_generate_last_error();
+        rep = zrep.text;
+    } else if (msg.empty() && total && ngsq_generate_write(g, o[0].write_fd, o[1].write_fd, a.seed, 0, total, a.batch_pairs, &rep) != NGSQ_OK)
         msg = ngsq_generate_last_error();
     for (int k = 0; k < 2; k++) {
         int e = 0;
@@ -201,5 +218,9 @@ int generate_main(int argc, char **argv, int at) {
                 (unsigned long long)rep.pairs, (unsigned long long)rep.batches, (unsigned long long)rep.text_bytes_one,
                 (unsigned long long)rep.rejected_start, (unsigned long long)rep.rejected_end, (unsigned long long)rep.rejected_base, rep.draw_ms,
                 rep.format_ms, rep.copy_ms, rep.write_ms, rep.total_ms);
+    if (g_level >= 3 && on_device)
+        fprintf(stderr, "[ngs] generate: BGZF on the device: %llu and %llu compressed bytes in %llu blocks (%llu stored), deflate %.1f ms\n",
+                (unsigned long long)zrep.compressed_bytes_one, (unsigned long long)zrep.compressed_bytes_two, (unsigned long long)zrep.blocks,
+                (unsigned long long)zrep.stored_blocks, zrep.deflate_ms);
     return 0;
 }

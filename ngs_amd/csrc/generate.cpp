@@ -9,6 +9,7 @@
 #include <memory>
 #include <unordered_set>
 
+#include "deflate_kernels.h"
 #include "generate_kernels.h"
 #include "reference_load.h"
 #include "sam_run.h"
@@ -203,10 +204,25 @@ int ngsq_generate_load(ngsq_generate *g, ngsq_ctx *c) {
     return NGSQ_OK;
 }
 
-int ngsq_generate_write(ngsq_generate *g, int fd_one, int fd_two, uint64_t seed, uint64_t first_pair, uint64_t n_pairs, uint64_t batch_pairs,
-                        ngsq_generate_report *out) {
+// bgzf: bit k set = file k receives BGZF (the batch's text compressed on the device in front of its writer), and the EOF block
+// at the end; ext (optional) receives what the encoder did.
+static int generate_write(ngsq_generate *g, int fd_one, int fd_two, uint64_t seed, uint64_t first_pair, uint64_t n_pairs, uint64_t batch_pairs,
+                          ngsq_generate_report *out, uint32_t bgzf, ngsq_generate_bgzf_report *ext) {
     if (!g || fd_one < 0 || fd_two < 0) return gfail(NGSQ_ERR_INVALID_ARGUMENT, "null argument");
     if (out) memset(out, 0, sizeof *out);
+    auto write_eof = [&](int k) -> int {
+        const int e = write_all(k ? fd_two : fd_one, reinterpret_cast<const char *>(BGZF_EOF_BLOCK), sizeof BGZF_EOF_BLOCK);
+        if (!e) return NGSQ_OK;
+        return gfail(NGSQ_ERR_INVALID_ARGUMENT, "could not write record to read %s file: %s (os error %d)", k ? "two" : "one", strerror(e), e);
+    };
+    if (bgzf && !n_pairs && first_pair <= (UINT64_MAX >> GEN_ERR_BITS)) { // (no pair: no device)
+        for (int k = 0; k < 2; k++)
+            if (bgzf >> k & 1) {
+                if (const int rc = write_eof(k)) return rc;
+                if (ext) (k ? ext->compressed_bytes_two : ext->compressed_bytes_one) = sizeof BGZF_EOF_BLOCK;
+            }
+        return NGSQ_OK;
+    }
     if (!g->ctx) return gfail(NGSQ_ERR_STATE, "ngsq_generate_load was not called");
     if (first_pair > (UINT64_MAX >> GEN_ERR_BITS) || n_pairs > (UINT64_MAX >> GEN_ERR_BITS) - first_pair)
         return gfail(NGSQ_ERR_LIMIT, "pair numbers are taken up to 2^56");
@@ -226,6 +242,19 @@ int ngsq_generate_write(ngsq_generate *g, int fd_one, int fd_two, uint64_t seed,
     MappedBuf hw;
     SamEvents ev; // ready[2]; draw a/b, write a/b
     SamWriter w[2];
+    // BGZF: the compressed batches [file][batch & 1], the encoder's arrays, the words it hands the host, its time
+    DevArray<uint8_t> d_comp[2][2];
+    DeflateScratch zsc[2];
+    MappedBuf zhw;
+    SamEvents zev; // [0], [1]: around a batch's encoder launches
+    uint64_t comp_bytes[2] = {0, 0}, z_blocks = 0, z_stored = 0;
+    double deflate_ms = 0;
+    if (bgzf) {
+        GHIP(zhw.reserve(2 * DEFLATE_HOST_WORDS * sizeof(unsigned long long)));
+        memset(zhw.h, 0, 2 * DEFLATE_HOST_WORDS * sizeof(unsigned long long));
+        GHIP(hipEventCreate(&zev.e[0]));
+        GHIP(hipEventCreate(&zev.e[1]));
+    }
     GHIP(d_pick.reserve(n0));
     GHIP(d_off.reserve(n0 + 1));
     GHIP(d_work.reserve(GEN_WORK_WORDS));
@@ -279,15 +308,42 @@ int ngsq_generate_write(ngsq_generate *g, int fd_one, int fd_two, uint64_t seed,
         // the buffers of batch k - 2 are this batch's once their copies have completed
         const uint32_t slot = (uint32_t)(batches & 1);
         if (batches >= 2 && (!w[0].wait_copied(batches - 1) || !w[1].wait_copied(batches - 1))) return NGSQ_OK; // (the writer's error is read at the end)
-        GHIP(d_text[0][slot].reserve(bytes + 1));
-        GHIP(d_text[1][slot].reserve(bytes + 1));
+        GHIP(d_text[0][slot].reserve(bytes + 1 + (bgzf ? DEFLATE_IN_SLACK : 0)));
+        GHIP(d_text[1][slot].reserve(bytes + 1 + (bgzf ? DEFLATE_IN_SLACK : 0)));
         GHIP(hipEventRecord(ev.e[4], st));
         GHIP(launch_gen_write(g->T, seed, first, n, d_pick.p, d_off.p, d_text[0][slot].p, d_text[1][slot].p, st));
         GHIP(hipEventRecord(ev.e[5], st));
+        const char *src[2] = {d_text[0][slot].p, d_text[1][slot].p};
+        uint64_t job_bytes[2] = {bytes, bytes};
+        if (bgzf && bytes) {
+            // the text of a compressed file stays on the device: its blocks are what the writer copies.  The host learns their
+            // size from the encoder's pinned words, so it waits for the batch here (the writers still work on the one before).
+            GHIP(hipEventRecord(zev.e[0], st));
+            for (int k = 0; k < 2; k++)
+                if (bgzf >> k & 1) {
+                    GHIP(d_comp[k][slot].reserve(deflate_bound(bytes)));
+                    GHIP(launch_bgzf_deflate(reinterpret_cast<const uint8_t *>(d_text[k][slot].p), bytes, d_comp[k][slot].p, zsc[k],
+                                             static_cast<unsigned long long *>(zhw.dev) + k * DEFLATE_HOST_WORDS, st));
+                }
+            GHIP(hipEventRecord(zev.e[1], st));
+            GHIP(hipEventSynchronize(zev.e[1]));
+            float zms = 0;
+            if (hipEventElapsedTime(&zms, zev.e[0], zev.e[1]) == hipSuccess) deflate_ms += zms;
+            for (int k = 0; k < 2; k++)
+                if (bgzf >> k & 1) {
+                    const unsigned long long *const zh = static_cast<const unsigned long long *>(zhw.h) + k * DEFLATE_HOST_WORDS;
+                    if (zh[DH_BYTES] > deflate_bound(bytes)) return gfail(NGSQ_ERR_STATE, "the encoder wrote more than its bound");
+                    src[k] = reinterpret_cast<const char *>(d_comp[k][slot].p);
+                    job_bytes[k] = zh[DH_BYTES];
+                    comp_bytes[k] += zh[DH_BYTES];
+                    z_blocks += deflate_blocks(bytes);
+                    z_stored += zh[DH_STORED];
+                }
+        }
         GHIP(hipEventRecord(ev.e[slot], st));
         write_pending = true;
-        w[0].push(SamJob{d_text[0][slot].p, bytes, ev.e[slot], batches});
-        w[1].push(SamJob{d_text[1][slot].p, bytes, ev.e[slot], batches});
+        w[0].push(SamJob{src[0], job_bytes[0], ev.e[slot], batches});
+        w[1].push(SamJob{src[1], job_bytes[1], ev.e[slot], batches});
         text_bytes += bytes;
         batches++;
         return NGSQ_OK;
@@ -311,6 +367,18 @@ int ngsq_generate_write(ngsq_generate *g, int fd_one, int fd_two, uint64_t seed,
             rc = gfail(NGSQ_ERR_INVALID_ARGUMENT, "could not write record to read %s file: %s (os error %d)", k ? "two" : "one", strerror(w[k].werr), w[k].werr);
     }
     if (rc != NGSQ_OK) (void)hipStreamSynchronize(st); // (the device buffers go back to the cache: nothing may still use them)
+    for (int k = 0; k < 2 && rc == NGSQ_OK && bad == ~0ull; k++)
+        if (bgzf >> k & 1) {
+            rc = write_eof(k);
+            comp_bytes[k] += sizeof BGZF_EOF_BLOCK;
+        }
+    if (ext) {
+        ext->compressed_bytes_one = comp_bytes[0];
+        ext->compressed_bytes_two = comp_bytes[1];
+        ext->blocks = z_blocks;
+        ext->stored_blocks = z_stored;
+        ext->deflate_ms = deflate_ms;
+    }
     if (rc == NGSQ_OK && bad != ~0ull) {
         const uint64_t pair = bad >> GEN_ERR_BITS;
         // which provider: the pair's first draw, as k_gen_draw makes it
@@ -338,6 +406,18 @@ int ngsq_generate_write(ngsq_generate *g, int fd_one, int fd_two, uint64_t seed,
         out->total_ms = now_ms() - t_begin;
     }
     return rc;
+}
+
+int ngsq_generate_write(ngsq_generate *g, int fd_one, int fd_two, uint64_t seed, uint64_t first_pair, uint64_t n_pairs, uint64_t batch_pairs,
+                        ngsq_generate_report *out) {
+    return generate_write(g, fd_one, fd_two, seed, first_pair, n_pairs, batch_pairs, out, 0, nullptr);
+}
+
+int ngsq_generate_write_bgzf(ngsq_generate *g, int fd_one, int fd_two, uint64_t seed, uint64_t first_pair, uint64_t n_pairs, uint64_t batch_pairs,
+                             uint32_t flags, ngsq_generate_bgzf_report *out) {
+    if (out) memset(out, 0, sizeof *out);
+    if (flags & ~(NGSQ_GENERATE_PLAIN_ONE | NGSQ_GENERATE_PLAIN_TWO)) return gfail(NGSQ_ERR_INVALID_ARGUMENT, "unknown flags 0x%x", flags);
+    return generate_write(g, fd_one, fd_two, seed, first_pair, n_pairs, batch_pairs, out ? &out->text : nullptr, 3u & ~flags, out);
 }
 
 } // extern "C"

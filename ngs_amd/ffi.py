@@ -269,6 +269,25 @@ class GenerateReport(C.Structure):
                 ("format_ms", C.c_double), ("copy_ms", C.c_double), ("write_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class GenerateBgzfReport(C.Structure):
+    _fields_ = [("text", GenerateReport), ("compressed_bytes_one", C.c_uint64), ("compressed_bytes_two", C.c_uint64),
+                ("blocks", C.c_uint64), ("stored_blocks", C.c_uint64), ("deflate_ms", C.c_double)]
+
+
+GENERATE_PLAIN_ONE, GENERATE_PLAIN_TWO = 1, 2
+
+# ---- include/ngsq_bgzf.h ----------------------------------------------------------------------
+BGZF_BLOCK_INPUT = 65280
+BGZF_EOF = 1
+BGZF_EOF_BLOCK = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
+
+class BgzfDeflateReport(C.Structure):
+    _fields_ = [("blocks", C.c_uint64), ("stored_blocks", C.c_uint64), ("in_bytes", C.c_uint64), ("out_bytes", C.c_uint64),
+                ("tokens", C.c_uint64), ("matches", C.c_uint64), ("deflate_ms", C.c_double), ("crc_ms", C.c_double),
+                ("pack_ms", C.c_double), ("copy_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 # ---- include/ngsq_derive.h --------------------------------------------------------------------
 DERIVE_INSTRUMENTS, DERIVE_FLOWCELLS = 0, 1
 
@@ -456,6 +475,11 @@ PROTOTYPES = {
     "ngsq_derive_lookup": (C.c_int, [C.c_int, C.c_char_p, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "ngsq_derive_predict": (C.c_int, [C.POINTER(C.c_char_p), u32p, C.c_uint64, C.POINTER(C.c_char_p), u32p, C.c_uint64, C.c_char_p,
                                       C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ngsq_generate_write_bgzf": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                           C.POINTER(GenerateBgzfReport)]),
+    # include/ngsq_bgzf.h
+    "ngsq_bgzf_deflate_bound": (C.c_uint64, [C.c_uint64, C.c_uint32]),
+    "ngsq_bgzf_deflate_device": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p, C.c_uint32, C.POINTER(BgzfDeflateReport)]),
     "ngsq_bgzf_inflate_device": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p, C.c_int]),
     # include/ngsq_comm.h
     "ngsq_comm_last_error": (C.c_char_p, [comm_p]),

@@ -735,19 +735,32 @@ class Generator:
             self._ctx = ctx
             _check_generate(self.lib.ngsq_generate_load(self._g, ctx), self.lib)
 
-    def write_fds(self, fd_one: int, fd_two: int, seed: int, n_pairs: int, first_pair: int = 0, batch_pairs: int = 0) -> Dict[str, float]:
+    def write_fds(self, fd_one: int, fd_two: int, seed: int, n_pairs: int, first_pair: int = 0, batch_pairs: int = 0,
+                  bgzf: bool = False, plain: int = 0) -> Dict[str, float]:
+        """bgzf: both descriptors receive BGZF compressed on the device (ngsq_generate_write_bgzf; `plain`: ffi.GENERATE_PLAIN_*
+        for a file that stays text); the report then also has the compressed bytes per file and the encoder's GPU time."""
+        if bgzf:
+            if n_pairs:
+                self.load()
+            zrep = ffi.GenerateBgzfReport()
+            _check_generate(self.lib.ngsq_generate_write_bgzf(self._g, fd_one, fd_two, seed, first_pair, n_pairs, batch_pairs, plain,
+                                                              C.byref(zrep)), self.lib)
+            out = {k: getattr(zrep.text, k) for k, _ in ffi.GenerateReport._fields_}
+            out.update({k: getattr(zrep, k) for k, _ in ffi.GenerateBgzfReport._fields_ if k != "text"})
+            return out
         self.load()
         rep = ffi.GenerateReport()
         _check_generate(self.lib.ngsq_generate_write(self._g, fd_one, fd_two, seed, first_pair, n_pairs, batch_pairs, C.byref(rep)), self.lib)
         return {k: getattr(rep, k) for k, _ in ffi.GenerateReport._fields_}
 
-    def write(self, path_one: str, path_two: str, seed: int, n_pairs: int, first_pair: int = 0, batch_pairs: int = 0, append: bool = False):
+    def write(self, path_one: str, path_two: str, seed: int, n_pairs: int, first_pair: int = 0, batch_pairs: int = 0, append: bool = False,
+              bgzf: bool = False):
         flags = os.O_WRONLY | os.O_CREAT | (os.O_APPEND if append else os.O_TRUNC)
         fd1 = os.open(path_one, flags, 0o666)
         try:
             fd2 = os.open(path_two, flags, 0o666)
             try:
-                return self.write_fds(fd1, fd2, seed, n_pairs, first_pair, batch_pairs)
+                return self.write_fds(fd1, fd2, seed, n_pairs, first_pair, batch_pairs, bgzf=bgzf)
             finally:
                 os.close(fd2)
         finally:
@@ -768,7 +781,30 @@ class Generator:
         self.close()
 
 
-def generate(providers, path_one: str, path_two: str, seed: int, n_pairs: int, first_pair: int = 0, batch_pairs: int = 0, device: int = 0, lib=None):
-    """One call of `ngs generate` in process: the report of Generator.write."""
+def generate(providers, path_one: str, path_two: str, seed: int, n_pairs: int, first_pair: int = 0, batch_pairs: int = 0, device: int = 0, lib=None,
+             bgzf: bool = False):
+    """One call of `ngs generate` in process: the report of Generator.write.  bgzf: both files are BGZF written on the device."""
     with Generator(providers, device=device, lib=lib) as g:
-        return g.write(path_one, path_two, seed, n_pairs, first_pair, batch_pairs)
+        return g.write(path_one, path_two, seed, n_pairs, first_pair, batch_pairs, bgzf=bgzf)
+
+
+def bgzf_deflate(data, device: int = 0, eof: bool = True, lib=None):
+    """(bytes, report): `data` as BGZF compressed on GPU `device` (include/ngsq_bgzf.h: ngsq_bgzf_deflate_device), blocks of
+    ffi.BGZF_BLOCK_INPUT input bytes, the EOF block behind them with eof."""
+    lib = lib or ffi.load_library()
+    data = bytes(data)
+    flags = ffi.BGZF_EOF if eof else 0
+    cfg = ffi.Config()
+    cfg.struct_size = C.sizeof(ffi.Config)
+    cfg.facets, cfg.device, cfg.n_refs = 0, device, 0
+    ctx = ffi.ctx_p()
+    _check(lib.ngsq_create(C.byref(cfg), C.byref(ctx)), None, lib)
+    try:
+        cap = lib.ngsq_bgzf_deflate_bound(len(data), flags)
+        out = np.empty(max(cap, 1), np.uint8)
+        n = C.c_uint64(0)
+        rep = ffi.BgzfDeflateReport()
+        _check(lib.ngsq_bgzf_deflate_device(ctx, data, len(data), out.ctypes.data, cap, C.byref(n), flags, C.byref(rep)), ctx, lib)
+        return bytes(out[:n.value]), {k: getattr(rep, k) for k, _ in ffi.BgzfDeflateReport._fields_}
+    finally:
+        lib.ngsq_destroy(ctx)
