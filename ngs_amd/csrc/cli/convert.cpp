@@ -1,11 +1,14 @@
 // convert.cpp -- `ngs convert` (src/convert/command.rs:26-172, src/convert/bam.rs:24-70): BAM to SAM, the
-// text formatted on the GPU by ngsq_bam_write_sam (include/ngsq_sam.h).  BAM to SAM only in this build.
+// text formatted on the GPU by ngsq_bam_write_sam (include/ngsq_sam.h); and, behind the additive `--gzip device`, SAM to BAM
+// (src/convert/sam.rs:26-90): the text parsed and the BGZF written on the GPU by ngsq_sam_write_bam
+// (include/ngsq_samtext.h).  Without the flag every command line answers as a build without that direction.
 #include <fcntl.h>
 
 #include <algorithm>
 #include <cerrno>
 
 #include "../../../include/ngsq_sam.h"
+#include "../../../include/ngsq_samtext.h"
 #include "cli.h"
 
 namespace {
@@ -13,6 +16,7 @@ namespace {
 struct ConvertArgs {
     std::vector<std::string> pos;
     bool has_n = false, has_fasta = false; // (-r and -c take no part in BAM to SAM, as in the reference)
+    bool gzip_device = false;              // --gzip device: SAM to BAM is converted, its BGZF written on the GPU
     unsigned long long n = 0;
     int device = 0;
 };
@@ -37,8 +41,12 @@ bool parse_args(int argc, char **argv, int at, ConvertArgs *a) {
                     "  -c, --compression-strategy <COMPRESSION_STRATEGY>\n"
                     "          [default: balanced] [possible values: best, balanced, fastest]\n"
                     "      --device <N>\n"
-                    "          GPU the SAM text is formatted on (additive, this build) [default: 0]\n\n"
-                    "This build converts BAM to SAM only.\n");
+                    "          GPU the SAM text is formatted on (additive, this build) [default: 0]\n"
+                    "      --gzip <WHERE>\n"
+                    "          Where BGZF output is compressed (additive, this build): `device` converts SAM to BAM on the GPU;\n"
+                    "          `host` changes nothing [default: host] [possible values: host, device]\n\n"
+                    "This build converts BAM to SAM, and with --gzip device SAM to BAM: the text is parsed and the BGZF blocks are\n"
+                    "written on the GPU, whose encoder has one setting (-c is checked and takes no part).\n");
             return false;
         } else if (s == "-n" || s == "--num-records") {
             const std::string v = val("--num-records <USIZE>");
@@ -57,10 +65,51 @@ bool parse_args(int argc, char **argv, int at, ConvertArgs *a) {
                 bail("invalid value '" + v + "' for '--compression-strategy <COMPRESSION_STRATEGY>' [possible values: best, balanced, fastest]");
         } else if (s == "--device") {
             a->device = atoi(val("--device <N>").c_str());
+        } else if (s == "--gzip") {
+            const std::string v = val("--gzip <WHERE>");
+            if (v == "host") a->gzip_device = false;
+            else if (v == "device") a->gzip_device = true;
+            else bail("invalid value '" + v + "' for '--gzip <WHERE>' [possible values: host, device]");
         } else if (!s.empty() && s[0] == '-' && s != "-") bail("unexpected argument '" + s + "' found");
         else a->pos.push_back(s);
     }
     return true;
+}
+
+// to_bam_async (sam.rs:26-90): (1) open the SAM and read its header, (2) create the BAM file, (3) the header, (4) every record
+int sam_to_bam(const ConvertArgs &a, const std::string &from, const std::string &to) {
+    char why[1024];
+    if (ngsq_sam_check_header(from.c_str(), nullptr, why, sizeof why) != NGSQ_OK) bail(why);
+    const int fd = open(to.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
+    if (fd < 0) {
+        const int e = errno;
+        bail(std::string("opening BAM output file: ") + strerror(e) + " (os error " + std::to_string(e) + ")");
+    }
+    ngsq_config cfg{};
+    cfg.struct_size = sizeof cfg;
+    cfg.device = a.device;
+    ngsq_ctx *ctx = nullptr;
+    if (ngsq_create(&cfg, &ctx) != NGSQ_OK) {
+        close(fd);
+        bail(ngsq_last_global_error());
+    }
+    const uint64_t max_records = a.has_n ? std::max<unsigned long long>(a.n, 1) : 0;
+    ngsq_samtext_report rep{};
+    const int rc = ngsq_sam_write_bam(ctx, from.c_str(), fd, max_records, 0, &rep);
+    const std::string msg = rc ? ngsq_last_error(ctx) : "";
+    const int close_rc = close(fd), close_errno = errno;
+    ngsq_destroy(ctx);
+    if (rc) bail(msg);
+    if (close_rc) bail(std::string("writing BAM record: ") + strerror(close_errno) + " (os error " + std::to_string(close_errno) + ")");
+    for (uint64_t m = 1; m <= rep.records / 1000000; m++) logf(2, "  [*] Processed %s records.", with_commas(m * 1000000).c_str());
+    if (g_level >= 3)
+        fprintf(stderr, "[ngs] convert: %llu records in %llu chunks, %llu header + %llu text bytes -> %llu BAM bytes in %llu blocks (%llu stored), "
+                        "%llu compressed; read %.1f ms, up %.1f ms, parse %.1f ms, deflate %.1f ms, down %.1f ms, write %.1f ms, total %.1f ms\n",
+                (unsigned long long)rep.records, (unsigned long long)rep.chunks, (unsigned long long)rep.header_bytes,
+                (unsigned long long)rep.text_bytes, (unsigned long long)rep.bam_bytes, (unsigned long long)rep.blocks,
+                (unsigned long long)rep.stored_blocks, (unsigned long long)rep.compressed_bytes, rep.read_ms, rep.h2d_ms, rep.parse_ms,
+                rep.deflate_ms, rep.d2h_ms, rep.write_ms, rep.total_ms);
+    return 0;
 }
 
 } // namespace
@@ -84,6 +133,7 @@ int convert_main(int argc, char **argv, int at) {
                       (ff == "CRAM" && tf == "BAM");
     const bool reference_only = (ff == "SAM" && tf == "BAM") || (ff == "GFF" && tf == "Block-gzipped GFF") || cram;
     if (cram && !a.has_fasta) bail("--reference-fasta is a required argument when converting to/from a CRAM file");
+    if (ff == "SAM" && tf == "BAM" && a.gzip_device) return sam_to_bam(a, from, to);
     if (reference_only)
         bail("Conversion from " + ff + " to " + tf + " is done by the reference `ngs convert` but not by this build, which converts BAM to SAM only");
     if (!(ff == "BAM" && tf == "SAM")) bail("Conversion from " + ff + " to " + tf + " is not currently supported");

@@ -561,6 +561,44 @@ def bam_to_sam(path: str, out_path: str, device: int = 0, max_records: int = 0, 
             os.close(fd)
 
 
+def sam_to_bam(path: str, out_path: str, device: int = 0, max_records: int = 0, chunk_bytes: int = 0, lib=None) -> Dict[str, float]:
+    """`ngs convert --gzip device <SAM> <BAM>` in process (include/ngsq_samtext.h): the BAM of the SAM text at `path` written to
+    out_path (created or truncated), the lines parsed and the BGZF blocks written on GPU `device`.  max_records: at most this
+    many records (0: all; the command line maps `-n N` to max(N, 1)); chunk_bytes: text bytes per chunk (0: the library's
+    default).  Returns the report; NgsqError on an open failure, a refused header or a line without a record."""
+    lib = lib or ffi.load_library()
+    why = C.create_string_buffer(1024)
+    rc = lib.ngsq_sam_check_header(path.encode(), None, why, len(why))   # (before any GPU work, and before out_path exists)
+    if rc != ffi.OK:
+        raise NgsqError(rc, why.value.decode("utf-8", "replace"))
+    cfg = ffi.Config()
+    cfg.struct_size = C.sizeof(ffi.Config)
+    cfg.facets, cfg.device, cfg.n_refs = 0, device, 0
+    ctx = ffi.ctx_p()
+    _check(lib.ngsq_create(C.byref(cfg), C.byref(ctx)), None, lib)
+    try:
+        fd = os.open(out_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o666)
+        try:
+            rep = ffi.SamTextReport()
+            _check(lib.ngsq_sam_write_bam(ctx, path.encode(), fd, max_records, chunk_bytes, C.byref(rep)), ctx, lib)
+            return {k: getattr(rep, k) for k, _ in ffi.SamTextReport._fields_}
+        finally:
+            os.close(fd)
+    finally:
+        lib.ngsq_destroy(ctx)
+
+
+def sam_parse_f32(text, lib=None) -> int:
+    """The bits of the f32 an `f` value of SAM text reads as (ngsq_sam_parse_f32: the kernels' parser, on the host)."""
+    lib = lib or ffi.load_library()
+    t = text.encode("latin-1") if isinstance(text, str) else bytes(text)
+    bits = C.c_uint32(0)
+    rc = lib.ngsq_sam_parse_f32(t, len(t), C.byref(bits))
+    if rc != ffi.OK:
+        raise NgsqError(rc, f"not an f32 value: {t!r}")
+    return bits.value
+
+
 def bam_query_chunks(path: str, query: str, bai_path: Optional[str] = None, lib=None):
     """The region and the merged chunks of a `ngs view` query (include/ngsq_view.h): (ref_id, start, end, [(begin, end), ...])
     with the 1-based inclusive interval (end = ffi.VIEW_END_MAX for one without an end) and the chunks' virtual offsets, from
