@@ -24,7 +24,7 @@ HEADERS = ["kernels.h", "context.h", "comm.h", "mem_pool.h", "bam_reader.h", "in
            "../../include/ngsq_shared.h", "../../include/ngsq_synth.h", "../../include/ngsq_bam.h", "../../include/ngsq_stage.h",
            "bai_kernels.h", "../../include/ngsq_index.h", "sam_kernels.h", "../../include/ngsq_sam.h",
            "derive_kernels.h", "../../include/ngsq_derive.h",
-           "sam_run.h", "view_kernels.h", "view_query.h", "../../include/ngsq_view.h",
+           "device_out.h", "sam_run.h", "view_kernels.h", "view_query.h", "../../include/ngsq_view.h",
            "generate_kernels.h", "generate_draw.h", "reference_load.h", "../../include/ngsq_generate.h",
            "samtext_kernels.h", "../../include/ngsq_samtext.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-result", "-fno-gpu-rdc"]

@@ -16,6 +16,7 @@
 #include "bai_kernels.h"
 #include "bgzf.h"
 #include "context.h"
+#include "device_out.h"
 #include "ingest_consumer.h"
 
 using namespace ngsq;
@@ -155,10 +156,7 @@ extern "C" int ngsq_bam_build_index(ngsq_bam *b, ngsq_ctx *c, const char *bai_pa
     std::vector<unsigned long long> lin;
     // Every way out below waits for the stream first: a gather or a copy may still be queued on it when an error returns,
     // and the arrays above go back to the block cache or the heap when they leave scope (declared behind them: it runs first).
-    struct StreamDrain {
-        hipStream_t s;
-        ~StreamDrain() { (void)hipStreamSynchronize(s); }
-    } drain{st};
+    StreamDrain drain{st};
     // ---- the scan: every batch of the device ingest, in file order
     uint64_t records = 0, runs = 0;
     uint32_t parity = 0;

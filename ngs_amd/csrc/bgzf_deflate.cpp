@@ -6,7 +6,7 @@
 #include <cstring>
 
 #include "context.h"
-#include "deflate_kernels.h"
+#include "device_out.h"
 
 using namespace ngsq;
 
@@ -21,14 +21,6 @@ int zfail(ngsq_ctx *c, int code, const char *fmt, ...) {
     if (c) c->err = buf;
     return code;
 }
-
-struct Events4 {
-    hipEvent_t e[6] = {};
-    ~Events4() {
-        for (auto x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
 
 } // namespace
 
@@ -56,17 +48,15 @@ int ngsq_bgzf_deflate_device(ngsq_ctx *c, const uint8_t *in, uint64_t in_len, ui
 #define ZHIP(expr)                                                                                     \
     do {                                                                                               \
         hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) {                                                                        \
-            (void)hipStreamSynchronize(st); /* (the arrays go back to the cache: nothing may use them) */ \
-            return zfail(c, NGSQ_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_));                  \
-        }                                                                                              \
+        if (e_ != hipSuccess) return zfail(c, NGSQ_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
         hipStream_t st = c->stream;
         ZHIP(hipSetDevice(c->device));
         DevArray<uint8_t> d_in, d_out;
         DeflateScratch sc;
         MappedBuf hw;
-        Events4 ev;
+        HipEvents<6> ev; // the encoder's four, and the brackets of the copies
+        StreamDrain drain{st}; // (behind the arrays: it runs first)
         ZHIP(d_in.reserve(in_len + DEFLATE_IN_SLACK));
         ZHIP(d_out.reserve(deflate_bound(in_len)));
         ZHIP(hw.reserve(DEFLATE_HOST_WORDS * sizeof(unsigned long long)));

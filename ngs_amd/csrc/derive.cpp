@@ -14,6 +14,7 @@
 #include "../../include/ngsq_derive.h"
 #include "context.h"
 #include "derive_kernels.h"
+#include "device_out.h"
 #include "ingest_consumer.h"
 
 using namespace ngsq;
@@ -290,20 +291,11 @@ extern "C" int ngsq_bam_derive_instrument(ngsq_bam *b, ngsq_ctx *c, uint64_t max
     memset(pin.h, 0, DERIVE_HOST_WORDS * sizeof(unsigned long long));
     static_cast<unsigned long long *>(pin.h)[0] = ~0ull;
     const unsigned long long *const pin_h = static_cast<const unsigned long long *>(pin.h);
-    struct Events {
-        hipEvent_t a = nullptr, b = nullptr;
-        ~Events() {
-            if (a) (void)hipEventDestroy(a);
-            if (b) (void)hipEventDestroy(b);
-        }
-    } ev;
-    BHIP(hipEventCreate(&ev.a));
-    BHIP(hipEventCreate(&ev.b));
+    HipEvents<2> ev; // around a batch's kernel
+    BHIP(hipEventCreate(&ev.e[0]));
+    BHIP(hipEventCreate(&ev.e[1]));
     // every way out below waits for the stream first: the arrays above go back to the block cache when they leave scope
-    struct StreamDrain {
-        hipStream_t s;
-        ~StreamDrain() { (void)hipStreamSynchronize(s); }
-    } drain{st};
+    StreamDrain drain{st};
     // ---- the scan: every batch of the device ingest, in file order
     uint64_t records = 0, batches = 0;
     double scan_ms = 0, kernel_ms = 0;
@@ -313,9 +305,9 @@ extern "C" int ngsq_bam_derive_instrument(ngsq_bam *b, ngsq_ctx *c, uint64_t max
     auto read_pending = [&]() -> int {
         if (!pending) return NGSQ_OK;
         pending = false;
-        BHIP(hipEventSynchronize(ev.b));
+        BHIP(hipEventSynchronize(ev.e[1]));
         float ms = 0;
-        if (hipEventElapsedTime(&ms, ev.a, ev.b) == hipSuccess) kernel_ms += ms;
+        if (hipEventElapsedTime(&ms, ev.e[0], ev.e[1]) == hipSuccess) kernel_ms += ms;
         if (pin_h[0] != ~0ull)
             return ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "Could not parse Illumina-formatted query names for read: %.*s", (int)pin_h[2],
                                  reinterpret_cast<const char *>(pin_h + 4));
@@ -337,9 +329,9 @@ extern "C" int ngsq_bam_derive_instrument(ngsq_bam *b, ngsq_ctx *c, uint64_t max
         if (const int rp = read_pending()) return rp;
         const uint64_t n = bt.n_records;
         if (!n) break;
-        BHIP(hipEventRecord(ev.a, st));
+        BHIP(hipEventRecord(ev.e[0], st));
         BHIP(launch_derive_names(bt, o, records, (uint32_t)(batches + 1), S, static_cast<unsigned long long *>(pin.dev), st));
-        BHIP(hipEventRecord(ev.b, st));
+        BHIP(hipEventRecord(ev.e[1], st));
         pending = true;
         records += n;
         batches++;

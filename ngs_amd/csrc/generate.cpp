@@ -1,18 +1,17 @@
 // generate.cpp -- include/ngsq_generate.h: `ngs generate`.  The host opens and measures the FASTAs
 // (no HIP), brings them to the device as letters (reference_load.h) beside the providers' tables, and then only launches:
 // k_gen_draw chooses and sizes every pair of a batch, the ingest's scan turns the sizes into offsets, k_gen_write writes both
-// files' text, and two writer threads (sam_run.h's, one per file) carry it through their pinned rings to the descriptors
-// while the next batch is drawn.  The host never sees a base.
+// files' text, and the output stage of device_out.h (one writer thread per file) carries it through pinned rings to the
+// descriptors while the next batch is drawn.  The host never sees a base.
 #include "../../include/ngsq_generate.h"
 
 #include <cstdarg>
 #include <memory>
 #include <unordered_set>
 
-#include "deflate_kernels.h"
+#include "device_out.h"
 #include "generate_kernels.h"
 #include "reference_load.h"
-#include "sam_run.h"
 
 using namespace ngsq;
 
@@ -210,10 +209,12 @@ static int generate_write(ngsq_generate *g, int fd_one, int fd_two, uint64_t see
                           ngsq_generate_report *out, uint32_t bgzf, ngsq_generate_bgzf_report *ext) {
     if (!g || fd_one < 0 || fd_two < 0) return gfail(NGSQ_ERR_INVALID_ARGUMENT, "null argument");
     if (out) memset(out, 0, sizeof *out);
-    auto write_eof = [&](int k) -> int {
-        const int e = write_all(k ? fd_two : fd_one, reinterpret_cast<const char *>(BGZF_EOF_BLOCK), sizeof BGZF_EOF_BLOCK);
-        if (!e) return NGSQ_OK;
+    auto write_failed = [](int k, int e) {
         return gfail(NGSQ_ERR_INVALID_ARGUMENT, "could not write record to read %s file: %s (os error %d)", k ? "two" : "one", strerror(e), e);
+    };
+    auto write_eof = [&](int k) -> int {
+        const int e = write_bgzf_eof(k ? fd_two : fd_one);
+        return e ? write_failed(k, e) : NGSQ_OK;
     };
     if (bgzf && !n_pairs && first_pair <= (UINT64_MAX >> GEN_ERR_BITS)) { // (no pair: no device)
         for (int k = 0; k < 2; k++)
@@ -240,18 +241,22 @@ static int generate_write(ngsq_generate *g, int fd_one, int fd_two, uint64_t see
     DevArray<char> d_text[2][2]; // [file][batch & 1]
     ScanScratch scan;
     MappedBuf hw;
-    SamEvents ev; // ready[2]; draw a/b, write a/b
-    SamWriter w[2];
-    // BGZF: the compressed batches [file][batch & 1], the encoder's arrays, the words it hands the host, its time
-    DevArray<uint8_t> d_comp[2][2];
-    DeflateScratch zsc[2];
+    HipEvents<4> ev; // draw a/b, write a/b
+    JobSlots slots; // of d_text and of the encoders' blocks: the two files share the batch
+    // BGZF: a file's encoder with its compressed batches [batch & 1], the words both hand the host, the time of a batch's launches
+    BgzfEncoder enc[2];
     MappedBuf zhw;
-    SamEvents zev; // [0], [1]: around a batch's encoder launches
-    uint64_t comp_bytes[2] = {0, 0}, z_blocks = 0, z_stored = 0;
+    HipEvents<2> zev;
     double deflate_ms = 0;
+    DeviceWriter w[2];     // (behind the buffers and events its copies use: its copy stream is drained before they go)
+    StreamDrain drain{st}; // (behind the arrays: it runs first)
     if (bgzf) {
         GHIP(zhw.reserve(2 * DEFLATE_HOST_WORDS * sizeof(unsigned long long)));
         memset(zhw.h, 0, 2 * DEFLATE_HOST_WORDS * sizeof(unsigned long long));
+        for (int k = 0; k < 2; k++) {
+            enc[k].h = static_cast<const unsigned long long *>(zhw.h) + k * DEFLATE_HOST_WORDS;
+            enc[k].hdev = static_cast<unsigned long long *>(zhw.dev) + k * DEFLATE_HOST_WORDS;
+        }
         GHIP(hipEventCreate(&zev.e[0]));
         GHIP(hipEventCreate(&zev.e[1]));
     }
@@ -266,37 +271,28 @@ static int generate_write(ngsq_generate *g, int fd_one, int fd_two, uint64_t see
         GHIP(hipMemcpyAsync(d_work.p, init, sizeof init, hipMemcpyHostToDevice, st));
         GHIP(hipStreamSynchronize(st));
     }
-    GHIP(hipEventCreateWithFlags(&ev.e[0], hipEventDisableTiming));
-    GHIP(hipEventCreateWithFlags(&ev.e[1], hipEventDisableTiming));
-    for (int k = 2; k < 6; k++) GHIP(hipEventCreate(&ev.e[k]));
-    for (int k = 0; k < 2; k++) {
-        w[k].fd = k ? fd_two : fd_one;
-        w[k].device = c->device;
-        GHIP(pool_stream_get(false, &w[k].cs));
-    }
-    for (int k = 0; k < 2; k++) {
-        SamWriter *wr = &w[k];
-        wr->th = std::thread([wr] { wr->run(); });
-    }
-    uint64_t batches = 0, done = 0, text_bytes = 0, bad = ~0ull;
+    GHIP(slots.create());
+    for (auto &e : ev.e) GHIP(hipEventCreate(&e));
+    for (int k = 0; k < 2; k++) GHIP(w[k].start(k ? fd_two : fd_one, c->device));
+    uint64_t done = 0, text_bytes = 0, bad = ~0ull;
     unsigned long long rej[3] = {0, 0, 0};
     double draw_ms = 0, format_ms = 0;
     bool write_pending = false;
     auto add_write_time = [&] {
         float ms = 0;
-        if (write_pending && hipEventElapsedTime(&ms, ev.e[4], ev.e[5]) == hipSuccess) format_ms += ms;
+        if (write_pending && hipEventElapsedTime(&ms, ev.e[2], ev.e[3]) == hipSuccess) format_ms += ms;
         write_pending = false;
     };
     // one batch; the function's HIP errors leave through `rc`, so that the writers are stopped below either way
     auto batch = [&](uint64_t first, uint64_t n) -> int {
-        GHIP(hipEventRecord(ev.e[2], st));
+        GHIP(hipEventRecord(ev.e[0], st));
         GHIP(launch_gen_draw(g->T, seed, first, n, d_pick.p, d_off.p, d_work.p, st));
         GHIP(scan.exclusive_scan(d_off.p, n + 1, st));
         GHIP(launch_gen_total(d_off.p, n, d_work.p, static_cast<unsigned long long *>(hw.dev), st));
-        GHIP(hipEventRecord(ev.e[3], st));
-        GHIP(hipEventSynchronize(ev.e[3]));
+        GHIP(hipEventRecord(ev.e[1], st));
+        GHIP(hipEventSynchronize(ev.e[1]));
         float ms = 0;
-        if (hipEventElapsedTime(&ms, ev.e[2], ev.e[3]) == hipSuccess) draw_ms += ms;
+        if (hipEventElapsedTime(&ms, ev.e[0], ev.e[1]) == hipSuccess) draw_ms += ms;
         add_write_time();
         const unsigned long long *const h = static_cast<const unsigned long long *>(hw.h);
         const uint64_t bytes = h[0];
@@ -305,14 +301,13 @@ static int generate_write(ngsq_generate *g, int fd_one, int fd_two, uint64_t see
             bad = h[1 + GW_BAD];
             return NGSQ_OK;
         }
-        // the buffers of batch k - 2 are this batch's once their copies have completed
-        const uint32_t slot = (uint32_t)(batches & 1);
-        if (batches >= 2 && (!w[0].wait_copied(batches - 1) || !w[1].wait_copied(batches - 1))) return NGSQ_OK; // (the writer's error is read at the end)
+        if (!slots.acquire(w, 2)) return NGSQ_OK; // (the writer's error is read at the end)
+        const uint32_t slot = slots.slot();
         GHIP(d_text[0][slot].reserve(bytes + 1 + (bgzf ? DEFLATE_IN_SLACK : 0)));
         GHIP(d_text[1][slot].reserve(bytes + 1 + (bgzf ? DEFLATE_IN_SLACK : 0)));
-        GHIP(hipEventRecord(ev.e[4], st));
+        GHIP(hipEventRecord(ev.e[2], st));
         GHIP(launch_gen_write(g->T, seed, first, n, d_pick.p, d_off.p, d_text[0][slot].p, d_text[1][slot].p, st));
-        GHIP(hipEventRecord(ev.e[5], st));
+        GHIP(hipEventRecord(ev.e[3], st));
         const char *src[2] = {d_text[0][slot].p, d_text[1][slot].p};
         uint64_t job_bytes[2] = {bytes, bytes};
         if (bgzf && bytes) {
@@ -320,36 +315,22 @@ static int generate_write(ngsq_generate *g, int fd_one, int fd_two, uint64_t see
             // size from the encoder's pinned words, so it waits for the batch here (the writers still work on the one before).
             GHIP(hipEventRecord(zev.e[0], st));
             for (int k = 0; k < 2; k++)
-                if (bgzf >> k & 1) {
-                    GHIP(d_comp[k][slot].reserve(deflate_bound(bytes)));
-                    GHIP(launch_bgzf_deflate(reinterpret_cast<const uint8_t *>(d_text[k][slot].p), bytes, d_comp[k][slot].p, zsc[k],
-                                             static_cast<unsigned long long *>(zhw.dev) + k * DEFLATE_HOST_WORDS, st));
-                }
+                if (bgzf >> k & 1) GHIP(enc[k].launch(slot, d_text[k][slot].p, bytes, st));
             GHIP(hipEventRecord(zev.e[1], st));
             GHIP(hipEventSynchronize(zev.e[1]));
             float zms = 0;
             if (hipEventElapsedTime(&zms, zev.e[0], zev.e[1]) == hipSuccess) deflate_ms += zms;
             for (int k = 0; k < 2; k++)
-                if (bgzf >> k & 1) {
-                    const unsigned long long *const zh = static_cast<const unsigned long long *>(zhw.h) + k * DEFLATE_HOST_WORDS;
-                    if (zh[DH_BYTES] > deflate_bound(bytes)) return gfail(NGSQ_ERR_STATE, "the encoder wrote more than its bound");
-                    src[k] = reinterpret_cast<const char *>(d_comp[k][slot].p);
-                    job_bytes[k] = zh[DH_BYTES];
-                    comp_bytes[k] += zh[DH_BYTES];
-                    z_blocks += deflate_blocks(bytes);
-                    z_stored += zh[DH_STORED];
-                }
+                if (bgzf >> k & 1)
+                    if (const char *m = enc[k].collect(slot, bytes, &src[k], &job_bytes[k])) return gfail(NGSQ_ERR_STATE, "%s", m);
         }
-        GHIP(hipEventRecord(ev.e[slot], st));
+        GHIP(slots.submit(w, 2, src, job_bytes, st));
         write_pending = true;
-        w[0].push(SamJob{src[0], job_bytes[0], ev.e[slot], batches});
-        w[1].push(SamJob{src[1], job_bytes[1], ev.e[slot], batches});
         text_bytes += bytes;
-        batches++;
         return NGSQ_OK;
     };
     int rc = NGSQ_OK;
-    while (rc == NGSQ_OK && done < n_pairs && bad == ~0ull && !w[0].werr && !w[1].werr && w[0].herr == hipSuccess && w[1].herr == hipSuccess) {
+    while (rc == NGSQ_OK && done < n_pairs && bad == ~0ull && !w[0].failed() && !w[1].failed()) {
         const uint64_t n = std::min(batch_pairs, n_pairs - done);
         rc = batch(first_pair + done, n);
         if (rc == NGSQ_OK && bad == ~0ull) done += n;
@@ -359,24 +340,21 @@ static int generate_write(ngsq_generate *g, int fd_one, int fd_two, uint64_t see
         if (e != hipSuccess) rc = gfail(NGSQ_ERR_DEVICE, "hipStreamSynchronize: %s", hipGetErrorString(e));
         add_write_time();
     }
-    w[0].stop();
-    w[1].stop();
+    const WriterEnd end[2] = {w[0].end(), w[1].end()};
     for (int k = 0; k < 2 && rc == NGSQ_OK; k++) {
-        if (w[k].herr != hipSuccess) rc = gfail(NGSQ_ERR_DEVICE, "copying the FASTQ text to the host: %s", hipGetErrorString(w[k].herr));
-        else if (w[k].werr)
-            rc = gfail(NGSQ_ERR_INVALID_ARGUMENT, "could not write record to read %s file: %s (os error %d)", k ? "two" : "one", strerror(w[k].werr), w[k].werr);
+        if (end[k].herr != hipSuccess) rc = gfail(NGSQ_ERR_DEVICE, "copying the FASTQ text to the host: %s", hipGetErrorString(end[k].herr));
+        else if (end[k].werr) rc = write_failed(k, end[k].werr);
     }
-    if (rc != NGSQ_OK) (void)hipStreamSynchronize(st); // (the device buffers go back to the cache: nothing may still use them)
     for (int k = 0; k < 2 && rc == NGSQ_OK && bad == ~0ull; k++)
         if (bgzf >> k & 1) {
             rc = write_eof(k);
-            comp_bytes[k] += sizeof BGZF_EOF_BLOCK;
+            enc[k].comp_bytes += sizeof BGZF_EOF_BLOCK;
         }
     if (ext) {
-        ext->compressed_bytes_one = comp_bytes[0];
-        ext->compressed_bytes_two = comp_bytes[1];
-        ext->blocks = z_blocks;
-        ext->stored_blocks = z_stored;
+        ext->compressed_bytes_one = enc[0].comp_bytes;
+        ext->compressed_bytes_two = enc[1].comp_bytes;
+        ext->blocks = enc[0].blocks + enc[1].blocks;
+        ext->stored_blocks = enc[0].stored + enc[1].stored;
         ext->deflate_ms = deflate_ms;
     }
     if (rc == NGSQ_OK && bad != ~0ull) {
@@ -398,7 +376,7 @@ static int generate_write(ngsq_generate *g, int fd_one, int fd_two, uint64_t see
         out->rejected_end = rej[1];
         out->rejected_base = rej[2];
         out->text_bytes_one = out->text_bytes_two = text_bytes;
-        out->batches = batches;
+        out->batches = slots.jobs;
         out->draw_ms = draw_ms;
         out->format_ms = format_ms;
         out->copy_ms = w[0].copy_ms + w[1].copy_ms;

@@ -54,7 +54,7 @@ extern "C" int ngsq_bam_write_sam(ngsq_bam *b, ngsq_ctx *c, int fd, uint64_t max
         out->records = r.records;
         out->header_bytes = head.size();
         out->text_bytes = r.text_bytes;
-        out->batches = r.batches;
+        out->batches = r.slots.jobs;
         out->scan_ms = r.scan_ms;
         out->format_ms = r.format_ms;
         out->copy_ms = r.w.copy_ms;

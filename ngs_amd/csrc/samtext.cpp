@@ -1,8 +1,8 @@
 // samtext.cpp -- include/ngsq_samtext.h: `ngs convert --gzip device <SAM> <BAM>`.  The host reads the
 // header (the leading '@' lines), builds the reference list and its hash table, and then only moves bytes: the text goes in
 // chunks that end on a newline through two pinned buffers to the device, samtext_kernel.hip finds the lines and turns them
-// into BAM records, the device DEFLATE encoder (deflate_kernels.h) makes BGZF blocks of them, and the writer thread of
-// sam_run.h carries the blocks through its pinned ring to the descriptor.  While chunk k is written and compressed the host
+// into BAM records, the device DEFLATE encoder (deflate_kernels.h) makes BGZF blocks of them, and the output stage of
+// device_out.h carries the blocks through its pinned ring to the descriptor.  While chunk k is written and compressed the host
 // reads chunk k + 1 and copies it up on a second stream; while chunk k + 1 is parsed the writer copies chunk k down and
 // writes it.  Per chunk the host reads four words: lines, record bytes, error word, compressed bytes.
 #include "../../include/ngsq_samtext.h"
@@ -12,8 +12,7 @@
 #include <cstdarg>
 #include <unordered_set>
 
-#include "deflate_kernels.h"
-#include "sam_run.h"
+#include "device_out.h"
 #include "samtext_kernels.h"
 
 using namespace ngsq;
@@ -161,14 +160,7 @@ struct PinnedText {
     }
 };
 
-struct Events {
-    hipEvent_t e[12] = {};
-    ~Events() {
-        for (auto x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
-enum Ev { EV_UP0 = 0, EV_UP1, EV_H0, EV_H1, EV_P0, EV_P1, EV_W0, EV_W1, EV_Z1, EV_READY0, EV_READY1, EV_N };
+enum Ev { EV_UP0 = 0, EV_UP1, EV_H0, EV_H1, EV_P0, EV_P1, EV_W0, EV_W1, EV_Z1, EV_N };
 
 enum HostWord : uint32_t { HW_LINES = 0, HW_BYTES, HW_BAD, HW_TEXT, HW_DEFLATE, HW_WORDS = HW_DEFLATE + DEFLATE_HOST_WORDS };
 
@@ -248,7 +240,7 @@ int ngsq_sam_write_bam(ngsq_ctx *c, const char *sam_path, int fd, uint64_t max_r
         setup[1 + n_refs] = names.size();
     }
 
-    // ---- the device side; every HIP error leaves through `rc`, so that the stream is drained before the arrays go back
+    // ---- the device side; every HIP error leaves through `rc`, so that the writer is stopped either way
 #define SHIP(expr)                                                                                  \
     do {                                                                                            \
         hipError_t e_ = (expr);                                                                     \
@@ -256,15 +248,17 @@ int ngsq_sam_write_bam(ngsq_ctx *c, const char *sam_path, int fd, uint64_t max_r
     } while (0)
     hipStream_t st = c->stream, up = nullptr;
     DevArray<uint64_t> d_setup, d_tiles, d_start, d_off, d_flist;
-    DevArray<uint8_t> d_fmark, d_text[2], d_rec, d_comp[2];
+    DevArray<uint8_t> d_fmark, d_text[2], d_rec;
     ScanScratch scan;
-    DeflateScratch zsc;
+    BgzfEncoder enc; // d_rec's bytes become the blocks of a job
+    JobSlots zslots; // of the encoder's blocks (d_text alternates with the chunks, apart from them)
     MappedBuf hw;
     PinnedText pin[2];
-    Events ev;
-    SamWriter w;
+    HipEvents<EV_N> ev;
+    DeviceWriter w;
+    StreamDrain drain{st}, drain_up{nullptr, true}; // (behind the arrays: they run first)
     const size_t pin_bytes = (size_t)chunk_bytes + 2 + ST_TEXT_SLACK;
-    uint64_t records = 0, text_bytes = 0, bam_bytes = 0, comp_bytes = 0, chunks = 0, jobs = 0, blocks = 0, stored = 0, bad = ~0ull;
+    uint64_t records = 0, text_bytes = 0, bam_bytes = 0, chunks = 0, bad = ~0ull;
     double read_ms = 0, h2d_ms = 0, parse_ms = 0, deflate_ms = 0;
     uint64_t file_at = H.body_at;
     size_t carry = 0; // bytes of the line the last chunk ended inside, at the front of the next buffer
@@ -310,37 +304,31 @@ int ngsq_sam_write_bam(ngsq_ctx *c, const char *sam_path, int fd, uint64_t max_r
         SHIP(hipEventRecord(ev.e[EV_UP0 + slot], up));
         return NGSQ_OK;
     };
-    // bytes of d_rec through the encoder into d_comp[jobs & 1]; push_job waits for it and hands the blocks to the writer
+    auto copy_failed = [&](hipError_t e) { return sfail(c, NGSQ_ERR_DEVICE, "copying the BGZF blocks to the host: %s", hipGetErrorString(e)); };
+    // bytes of d_rec through the encoder into its buffer of the job's slot; push_job waits for it and hands the blocks to the writer
     auto compress = [&](uint64_t bytes) -> int {
-        const uint32_t zs = (uint32_t)(jobs & 1);
-        // the blocks of job k - 2 lie where this job's go: their copies must have completed
-        if (jobs >= 2 && !w.wait_copied(jobs - 1)) return sfail(c, NGSQ_ERR_DEVICE, "copying the BGZF blocks to the host: %s", hipGetErrorString(w.herr));
-        SHIP(d_comp[zs].reserve(deflate_bound(bytes)));
-        unsigned long long *const hdev = static_cast<unsigned long long *>(hw.dev);
-        SHIP(launch_bgzf_deflate(d_rec.p, bytes, d_comp[zs].p, zsc, hdev + HW_DEFLATE, st));
+        if (!zslots.acquire(&w)) return copy_failed(w.herr);
+        SHIP(enc.launch(zslots.slot(), d_rec.p, bytes, st));
         SHIP(hipEventRecord(ev.e[EV_Z1], st));
-        SHIP(hipEventRecord(ev.e[EV_READY0 + zs], st));
         return NGSQ_OK;
     };
     auto push_job = [&](uint64_t bytes) -> int {
-        const uint32_t zs = (uint32_t)(jobs & 1);
         SHIP(hipEventSynchronize(ev.e[EV_Z1]));
-        const unsigned long long *const zh = static_cast<const unsigned long long *>(hw.h) + HW_DEFLATE;
-        if (zh[DH_BYTES] > deflate_bound(bytes)) return sfail(c, NGSQ_ERR_STATE, "the encoder wrote more than its bound");
+        const char *blocks = nullptr;
+        uint64_t n = 0;
+        if (const char *m = enc.collect(zslots.slot(), bytes, &blocks, &n)) return sfail(c, NGSQ_ERR_STATE, "%s", m);
         float ms = 0;
         if (hipEventElapsedTime(&ms, ev.e[EV_W1], ev.e[EV_Z1]) == hipSuccess) deflate_ms += ms;
-        w.push(SamJob{reinterpret_cast<const char *>(d_comp[zs].p), zh[DH_BYTES], ev.e[EV_READY0 + zs], jobs});
-        jobs++;
+        // (nothing may be queued on st between compress and here: `ready` would cover it and hold the copy back)
+        SHIP(zslots.submit(w, blocks, n, st));
         bam_bytes += bytes;
-        comp_bytes += zh[DH_BYTES];
-        blocks += deflate_blocks(bytes);
-        stored += zh[DH_STORED];
         return NGSQ_OK;
     };
 
     auto run = [&]() -> int {
         SHIP(hipSetDevice(c->device));
         SHIP(pool_stream_get(false, &up));
+        drain_up.s = up;
         SHIP(d_setup.reserve(setup.size() + (names.size() + 7) / 8));
         SHIP(hipMemcpyAsync(d_setup.p, setup.data(), setup.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
         if (!names.empty()) SHIP(hipMemcpyAsync(d_setup.p + setup.size(), names.data(), names.size(), hipMemcpyHostToDevice, st));
@@ -357,15 +345,14 @@ int ngsq_sam_write_bam(ngsq_ctx *c, const char *sam_path, int fd, uint64_t max_r
             SHIP(hipHostMalloc(&p, pin_bytes, hipHostMallocDefault));
             pin[k].p = static_cast<char *>(p);
         }
+        enc.h = h + HW_DEFLATE;
+        enc.hdev = hdev + HW_DEFLATE;
         for (int k = 0; k < EV_N; k++) {
-            if (k == EV_UP0 || k == EV_UP1 || k == EV_READY0 || k == EV_READY1) SHIP(hipEventCreateWithFlags(&ev.e[k], hipEventDisableTiming));
+            if (k == EV_UP0 || k == EV_UP1) SHIP(hipEventCreateWithFlags(&ev.e[k], hipEventDisableTiming));
             else SHIP(hipEventCreate(&ev.e[k]));
         }
-        w.fd = fd;
-        w.device = c->device;
-        SHIP(pool_stream_get(false, &w.cs));
-        SamWriter *wr = &w;
-        w.th = std::thread([wr] { wr->run(); });
+        SHIP(zslots.create());
+        SHIP(w.start(fd, c->device));
         // the header's blocks, in front of the first record (as samtools writes them)
         SHIP(d_rec.reserve(hs.size() + DEFLATE_IN_SLACK));
         SHIP(hipMemcpyAsync(d_rec.p, hs.data(), hs.size(), hipMemcpyHostToDevice, st));
@@ -377,7 +364,7 @@ int ngsq_sam_write_bam(ngsq_ctx *c, const char *sam_path, int fd, uint64_t max_r
         if (const int rc = fill(0, &len)) return rc;
         if (len)
             if (const int rc = upload(0, len)) return rc;
-        while (len && !w.werr && w.herr == hipSuccess) {
+        while (len && !w.failed()) {
             const uint32_t slot = (uint32_t)(chunks & 1);
             // line starts
             const uint64_t tiles = samtext_tiles(len);
@@ -444,34 +431,29 @@ int ngsq_sam_write_bam(ngsq_ctx *c, const char *sam_path, int fd, uint64_t max_r
         return NGSQ_OK;
     };
     int rc = run();
-    if (rc != NGSQ_OK) {
-        (void)hipStreamSynchronize(st); // (the device buffers go back to the cache: nothing may still use them)
-        if (up) (void)hipStreamSynchronize(up);
-    }
-    w.stop();
-    if (up) pool_stream_put(false, up);
 #undef SHIP
-    if (rc == NGSQ_OK && w.herr != hipSuccess) rc = sfail(c, NGSQ_ERR_DEVICE, "copying the BGZF blocks to the host: %s", hipGetErrorString(w.herr));
-    if (rc == NGSQ_OK && w.werr) rc = sfail(c, NGSQ_ERR_INVALID_ARGUMENT, "writing BAM record: %s (os error %d)", strerror(w.werr), w.werr);
+    auto write_failed = [&](int e) { return sfail(c, NGSQ_ERR_INVALID_ARGUMENT, "writing BAM record: %s (os error %d)", strerror(e), e); };
+    const WriterEnd end = w.end();
+    if (rc == NGSQ_OK && end.herr != hipSuccess) rc = copy_failed(end.herr);
+    if (rc == NGSQ_OK && end.werr) rc = write_failed(end.werr);
     if (rc == NGSQ_OK && bad != ~0ull)
         rc = sfail(c, NGSQ_ERR_MALFORMED_RECORD, "reading SAM record: record %llu: %s", (unsigned long long)(bad >> ST_ERR_BITS),
                    samtext_error_text((uint32_t)(bad & ((1u << ST_ERR_BITS) - 1))));
     if (rc == NGSQ_OK && !long_line.empty())
         rc = sfail(c, NGSQ_ERR_LIMIT, "reading SAM record: record %llu: %s", (unsigned long long)records, long_line.c_str());
     if (rc == NGSQ_OK) {
-        const int e = write_all(fd, reinterpret_cast<const char *>(BGZF_EOF_BLOCK), sizeof BGZF_EOF_BLOCK);
-        if (e) rc = sfail(c, NGSQ_ERR_INVALID_ARGUMENT, "writing BAM record: %s (os error %d)", strerror(e), e);
-        comp_bytes += sizeof BGZF_EOF_BLOCK;
+        if (const int e = write_bgzf_eof(fd)) rc = write_failed(e);
+        enc.comp_bytes += sizeof BGZF_EOF_BLOCK;
     }
     if (out) {
         out->records = records;
         out->header_bytes = H.text.size();
         out->text_bytes = text_bytes;
         out->bam_bytes = bam_bytes;
-        out->compressed_bytes = comp_bytes;
+        out->compressed_bytes = enc.comp_bytes;
         out->chunks = chunks;
-        out->blocks = blocks;
-        out->stored_blocks = stored;
+        out->blocks = enc.blocks;
+        out->stored_blocks = enc.stored;
         out->read_ms = read_ms;
         out->h2d_ms = h2d_ms;
         out->parse_ms = parse_ms;

@@ -57,13 +57,9 @@ struct ViewRun {
     DevArray<ngsq_view_chunk> d_chunks;
     DevArray<uint8_t> d_keep;
     DevArray<unsigned long long> d_kept;
-    hipEvent_t sel[2] = {};
+    HipEvents<2> sel;
     double select_ms = 0;
     uint64_t scanned = 0, ranges = 0;
-    ~ViewRun() {
-        for (auto e : sel)
-            if (e) (void)hipEventDestroy(e);
-    }
 };
 
 // The 0-based index in the file of the record at virtual offset v: the records in front of it, counted by a walk from the
@@ -103,9 +99,9 @@ int walk(ViewRun &vr, const ViewRegion *region, uint64_t batch_records, bool *mo
         if (region) {
             // (the formatter's write pass of the batch in front may still read keep: the stream orders the two)
             BHIP(vr.d_keep.reserve(bt.n_records));
-            BHIP(hipEventRecord(vr.sel[0], r.st));
+            BHIP(hipEventRecord(vr.sel.e[0], r.st));
             BHIP(launch_view_select(bt, *region, vr.d_keep.p, vr.d_kept.p, r.st));
-            BHIP(hipEventRecord(vr.sel[1], r.st));
+            BHIP(hipEventRecord(vr.sel.e[1], r.st));
             keep = vr.d_keep.p;
         }
         uint64_t bad = ~0ull;
@@ -113,7 +109,7 @@ int walk(ViewRun &vr, const ViewRegion *region, uint64_t batch_records, bool *mo
         if (rc) break;
         if (region) { // (format_batch has waited for the stream)
             float ms = 0;
-            if (hipEventElapsedTime(&ms, vr.sel[0], vr.sel[1]) == hipSuccess) vr.select_ms += ms;
+            if (hipEventElapsedTime(&ms, vr.sel.e[0], vr.sel.e[1]) == hipSuccess) vr.select_ms += ms;
         }
         if (bad != ~0ull) {
             uint64_t index = bad >> SAM_ERR_BITS; // in the walk
@@ -181,7 +177,7 @@ extern "C" int ngsq_bam_view(ngsq_bam *b, ngsq_ctx *c, int fd, const char *query
         if (!q.chunks.empty())
             BHIP(hipMemcpyAsync(vr.d_chunks.p, q.chunks.data(), q.chunks.size() * sizeof(ngsq_view_chunk), hipMemcpyHostToDevice, r.st));
         BHIP(hipStreamSynchronize(r.st));
-        for (auto &e : vr.sel) BHIP(hipEventCreate(&e));
+        for (auto &e : vr.sel.e) BHIP(hipEventCreate(&e));
         BHIP(vr.d_keep.reserve(batch_records));
         region.chunks = vr.d_chunks.p;
         region.n_chunks = (uint32_t)q.chunks.size();
@@ -224,7 +220,7 @@ extern "C" int ngsq_bam_view(ngsq_bam *b, ngsq_ctx *c, int fd, const char *query
         out->text_bytes = r.text_bytes;
         out->chunks = q.chunks.size();
         out->ranges = vr.ranges;
-        out->batches = r.batches;
+        out->batches = r.slots.jobs;
         out->scan_ms = r.scan_ms;
         out->select_ms = vr.select_ms;
         out->format_ms = r.format_ms;

@@ -209,6 +209,34 @@ def test_a_run_longer_than_one_ring_slot(gpu_lib, base_fa, tmp_path):
     assert len(want.one) > (32 << 20) and rep["batches"] == 1
 
 
+def test_a_job_longer_than_the_whole_ring(gpu_lib, base_fa, tmp_path):
+    """420 000 pairs of 150 bases in one batch: each file's single job passes the writer's four 32 MiB slots, so a slot of
+    the ring is filled again while the job is still being copied.  Held by SHA-256 against the same pairs in batches of
+    2^15, the path the model tests pin (the Python model over 420 000 pairs would take minutes)."""
+    import hashlib
+    specs, n = [(base_fa, 10_000, 200.0, 30.0, 150, 1)], 420_000
+
+    def digests(batch, tag):
+        p1, p2 = str(tmp_path / f"{tag}_1.fastq"), str(tmp_path / f"{tag}_2.fastq")
+        rep = host.generate(specs, p1, p2, 17, n, batch_pairs=batch, lib=gpu_lib)
+        out = []
+        for p in (p1, p2):
+            h = hashlib.sha256()
+            with open(p, "rb") as f:
+                for piece in iter(lambda: f.read(1 << 24), b""):
+                    h.update(piece)
+            out.append((os.path.getsize(p), h.hexdigest()))
+            os.remove(p)
+        return out, rep
+
+    big, rep = digests(0, "whole")
+    assert rep["batches"] == 1 and rep["pairs"] == n
+    assert all(size > 4 * (32 << 20) for size, _ in big), big
+    small, rep = digests(1 << 15, "small")
+    assert rep["batches"] == -(-n // (1 << 15))
+    assert big == small
+
+
 def test_no_pairs(gpu_lib, base_fa, tmp_path):
     one, two, rep = device_files(gpu_lib, [(base_fa, 100, 10.0, 2.0, 36, 1)], tmp_path, seed=1, n=0)
     assert one == b"" and two == b"" and rep["pairs"] == 0 and rep["batches"] == 0

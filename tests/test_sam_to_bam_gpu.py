@@ -84,6 +84,25 @@ def test_hand_text(gpu_lib, tmp_path):
     assert rep["records"] == 4 and rep["header_bytes"] == len(want["header_text"])
 
 
+def test_a_failed_write_ends_the_call_with_its_message(gpu_lib, tmp_path):
+    """/dev/full refuses every write.  In one chunk the error is read at the end of the run; in chunks of 200 bytes (five jobs:
+    the header's and one per record) the wait for the copies of job k - 2 may meet a writer that has already failed (when
+    the chunk loop has not seen the failure first), and the call still returns.  The suite has no in-process time limit of
+    its own (only subprocess timeouts), so faulthandler ends the process if the call hangs."""
+    import faulthandler
+    src = os.path.join(GOLDEN, "hand_text.sam")
+    _, rep, _ = convert(gpu_lib, open(src, "rb").read(), tmp_path, chunk_bytes=200)
+    assert rep["chunks"] == 4   # (with the header's job: five jobs)
+    faulthandler.dump_traceback_later(120, exit=True)
+    try:
+        for chunk in (0, 200):
+            with pytest.raises(host.NgsqError) as e:
+                host.sam_to_bam(src, "/dev/full", chunk_bytes=chunk, lib=gpu_lib)
+            assert "writing BAM record: No space left on device (os error 28)" in str(e.value), chunk
+    finally:
+        faulthandler.cancel_dump_traceback_later()
+
+
 def test_hand_spec_and_long_cigar(gpu_lib, tmp_path):
     check(gpu_lib, hand_spec_text(), tmp_path, chunk_bytes=1 << 16)
     check(gpu_lib, sm.expected_sam(os.path.join(GOLDEN, "hand_longcigar.bam")), tmp_path)
