@@ -315,6 +315,13 @@ int ngsq_create(const ngsq_config *cfg, ngsq_ctx **out) {
         sa.bin_size = c->cfg.bin_size;
         sa.cov_cap = c->cfg.cov_cap;
         sa.head_guard = c->cfg.cov_head_guard;
+        sa.run_next = c->d_stream_u32 + 7 * nr4 + 2;
+        // the side stream of launch_all: the context's own also beside a caller's stream, at that stream's priority
+        int prio = 0;
+        CTX_TRY(hipStreamGetPriority(c->stream, &prio));
+        CTX_TRY(hipStreamCreateWithPriority(&c->side_stream, hipStreamNonBlocking, prio));
+        CTX_TRY(hipEventCreateWithFlags(&c->side_fork, hipEventDisableTiming));
+        CTX_TRY(hipEventCreateWithFlags(&c->side_join, hipEventDisableTiming));
         CTX_TRY(hipMemsetAsync(c->d_stream_u32, 0, (7 * nr4 + 4) * 4, c->stream));
         CTX_TRY(hipMemsetAsync(sa.plan_a, 0xFF, nr4 * 4, c->stream));
         CTX_TRY(hipMemsetAsync(c->d_last_key, 0, 8, c->stream));
@@ -390,6 +397,12 @@ void ngsq_destroy(ngsq_ctx *c) {
     ngsq::reference_abandon(c); // (a reference load still on its way writes into this context's buffers)
     (void)ngsq::pool_trim(); // blocks a finished device ingest left for the next file (mem_pool.h)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    if (c->side_stream) { // (joined to `stream` in every batch; a launch that failed between fork and join has waited for it)
+        (void)hipStreamSynchronize(c->side_stream);
+        (void)hipStreamDestroy(c->side_stream);
+    }
+    if (c->side_fork) (void)hipEventDestroy(c->side_fork);
+    if (c->side_join) (void)hipEventDestroy(c->side_join);
     (void)hipFree(c->d_ft_idx);
     (void)hipFree(c->d_ft_starts);
     (void)hipFree(c->d_ft_stops);
@@ -595,6 +608,11 @@ static int launch_all(ngsq_ctx *c, const DeviceBatch &db, const ColumnSizes &cs,
     const uint64_t n = db.n;
     const uint32_t rec_f = (pass_mask & NGSQ_PASS_RECORD) ? (facets & NGSQ_FACETS_RECORD_BASED) : 0;
     const uint32_t seq_f = (pass_mask & NGSQ_PASS_SEQUENCE) ? (facets & NGSQ_FACETS_SEQUENCE_BASED) : 0;
+    // GC Content and Edits in one pass of the batch: k_edits_rows tallies the GC window from the sequence bytes it compares (the
+    // column -- 75 of a record's 254 bytes -- is read once instead of twice; get_qc_facets builds both facets for one scan: qc.rs:44-126)
+    const bool gc_in_edits = (rec_f & NGSQ_FACET_GC_CONTENT) && (seq_f & NGSQ_FACET_EDITS) && edits_can_take_gc(c->st, db);
+    // streamed Coverage and a k_gc of its own in a batch with records: the two run side by side (below)
+    const bool corun = (seq_f & NGSQ_FACET_COVERAGE) && c->stream_cov && (rec_f & NGSQ_FACET_GC_CONTENT) && !gc_in_edits && n;
     if ((rec_f & (NGSQ_FACET_GENERAL | NGSQ_FACET_TEMPLATE_LENGTH)) || (seq_f & NGSQ_FACET_COVERAGE)) {
         const bool walk = (rec_f & NGSQ_FACET_GENERAL) || (seq_f & NGSQ_FACET_COVERAGE);
         const bool cov = (seq_f & NGSQ_FACET_COVERAGE) != 0;
@@ -621,18 +639,40 @@ static int launch_all(ngsq_ctx *c, const DeviceBatch &db, const ColumnSizes &cs,
             HIP_TRY(c, launch_fields(c->li, c->st, db, rec_f, cov ? (c->stream_cov ? 2 : 1) : 0, c->stream));
         }
         if (cov && c->stream_cov) {
-            // (on a stream of its own beside k_gc / k_qual it hides its 0.7 ms and costs k_qual_perm 1.2: DESIGN appendix A.8; confined to
-            // 16-96 compute units by a CU mask, with or without the other kernels kept off them, 5.74-16.7 ms per step against 5.55: A.9)
-            Bracket br(c, K_COV_STREAM, n * 8); // pos + cov_end of every record
-            HIP_TRY(c, launch_cov_stream(c->li, c->st, db, c->csa, c->stream));
+            // The two plan kernels stay on the context's stream: microseconds with nothing else resident, a millisecond when they
+            // queue for a wave slot behind a k_gc that fills every CU (DESIGN appendix A.9).
+            HIP_TRY(c, launch_cov_plan(c->st, db, c->csa, c->stream));
+            if (corun) {
+                // k_cov_stream (0.7 ms of scalar, vector and LDS work on 0.9 GB) inside the time k_gc waits for HBM: forked here, joined
+                // in front of k_qual_perm, which needs every CU whole (A.8) -- so the next batch's k_fields, and whatever drains the
+                // context's stream, is ordered behind it as well.  Both kernels are persistent and launched with grids that add up to
+                // one CU's wave slots and registers.
+                HIP_TRY(c, hipEventRecord(c->side_fork, c->stream));
+                HIP_TRY(c, hipStreamWaitEvent(c->side_stream, c->side_fork, 0));
+                hipError_t e;
+                {
+                    Bracket br(c, K_COV_STREAM, n * 8, c->side_stream);
+                    e = launch_cov_stream(c->li, c->st, db, c->csa, true, c->side_stream);
+                }
+                if (e == hipSuccess) {
+                    Bracket br(c, K_GC, n * 6 + cs.seq_bytes);
+                    e = launch_gc(c->li, c->st, db, cs.seq_bytes, true, c->stream);
+                }
+                if (e == hipSuccess) e = hipEventRecord(c->side_join, c->side_stream);
+                if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, c->side_join, 0);
+                if (e != hipSuccess) { // no join on the stream: nothing may be left running on the side when this returns
+                    (void)hipStreamSynchronize(c->side_stream);
+                    return fail(c, NGSQ_ERR_DEVICE, "streamed Coverage beside GC Content failed: %s", hipGetErrorString(e));
+                }
+            } else {
+                Bracket br(c, K_COV_STREAM, n * 8); // pos + cov_end of every record
+                HIP_TRY(c, launch_cov_stream(c->li, c->st, db, c->csa, false, c->stream));
+            }
         }
     }
-    // GC Content and Edits in one pass of the batch: k_edits_rows tallies the GC window from the sequence bytes it compares (the
-    // column -- 75 of a record's 254 bytes -- is read once instead of twice; get_qc_facets builds both facets for one scan: qc.rs:44-126)
-    const bool gc_in_edits = (rec_f & NGSQ_FACET_GC_CONTENT) && (seq_f & NGSQ_FACET_EDITS) && edits_can_take_gc(c->st, db);
-    if ((rec_f & NGSQ_FACET_GC_CONTENT) && !gc_in_edits) {
+    if ((rec_f & NGSQ_FACET_GC_CONTENT) && !gc_in_edits && !corun) {
         Bracket br(c, K_GC, n * 6 + cs.seq_bytes);
-        HIP_TRY(c, launch_gc(c->li, c->st, db, cs.seq_bytes, c->stream));
+        HIP_TRY(c, launch_gc(c->li, c->st, db, cs.seq_bytes, false, c->stream));
     }
     if (rec_f & NGSQ_FACET_QUALITY_SCORE) {
         Bracket br(c, K_QUAL, cs.qual_bytes);

@@ -101,9 +101,13 @@ struct ngsq_ctx {
     bool stream_cov = false;
     uint32_t *d_cov_end = nullptr;
     uint64_t cov_end_cap = 0;
-    uint32_t *d_stream_u32 = nullptr; // end_acc | prev_end | plan_a | plan_z | plan_h | plan_t | guard_until (n_refs each) | batch_span
+    uint32_t *d_stream_u32 = nullptr; // end_acc | prev_end | plan_a | plan_z | plan_h | plan_t | guard_until (n_refs each) | batch_span [2] | run_next
     unsigned long long *d_last_key = nullptr;
     uint32_t span_turn = 0;           // which of the two largest-span words the next batch uses (launch_all)
+    // k_cov_stream beside k_gc (launch_all): a stream of the context's own, forked from and joined to `stream` within one batch --
+    // whatever waits for `stream` afterwards has waited for it too
+    hipStream_t side_stream = nullptr;
+    hipEvent_t side_fork = nullptr, side_join = nullptr;
     uint8_t *d_chunk_flags = nullptr;
     ngsq::CovStreamArgs csa{};
     // Genomic Features gene model (ngsq_set_features)

@@ -23,7 +23,7 @@
 // A tile must also see the records of EARLIER tiles that reach into its positions.  A wave works through
 // consecutive tiles and carries their ends forward in an LDS list (everything in front with end > first
 // owned position: about one entry per unit of depth); the list is filtered and extended with the tile's own
-// records after each tile.  Without a valid list -- the first tile of a wave, after a sequence boundary, an
+// records after each tile.  Without a valid list -- the first tile of a wave's run, after a sequence boundary, an
 // empty tile or a pile deeper than the list -- the tile walks back through the (pos, cov_end) columns, 64
 // records at a time, until a group's first record cannot reach any more (start + largest span of the batch
 // <= first owned position) or lies on another sequence, and rebuilds the list from what it found.
@@ -100,6 +100,7 @@ __global__ __launch_bounds__(256) void k_cov_plan_refs(DeviceState st, CovStream
     // the NEXT batch's largest-span word (the batches use two words in turn): last read by the previous batch's k_cov_stream,
     // next written by the next batch's k_fields -- no memset per batch
     if (r == 0 && a.span_next) *a.span_next = 0;
+    if (r == 0) *a.run_next = 0; // the runs of this batch's k_cov_stream (the previous batch's has finished: context.cpp launch_all)
     if (r >= st.n_refs) return;
     const uint32_t pa = a.plan_a[r], pz = a.plan_z[r], prev = a.prev_end[r];
     const uint32_t acc = st.end_acc[r];
@@ -163,8 +164,10 @@ struct StTileIn {
     int32_t rf_t, ps_t, rf_n, ps_n;  // first record of the tile and of its successor
 };
 
-constexpr uint32_t ST_MIN_BLOCKS = 4;
-__global__ __launch_bounds__(ST_THREADS, ST_MIN_BLOCKS) void k_cov_stream(DeviceState st, DeviceBatch b, CovStreamArgs a) {
+// CORUN: the launch shares every CU with k_gc (launch_cov_stream): the wave takes runs of tiles from a counter for as long as there
+// are any, instead of one share fixed by the grid.
+template <bool CORUN>
+__device__ __forceinline__ void cov_stream_body(const DeviceState &st, const DeviceBatch &b, const CovStreamArgs &a, uint32_t run_len) {
     NGSQ_FOREGROUND_WAVE();
     extern __shared__ __attribute__((aligned(16))) uint32_t s_dyn[];
     const uint32_t nb = a.cov_cap + 2;
@@ -184,10 +187,6 @@ __global__ __launch_bounds__(ST_THREADS, ST_MIN_BLOCKS) void k_cov_stream(Device
 
     const uint64_t n_wt = (b.n + CS_TILE - 1) / CS_TILE;
     const uint64_t n_full = b.n / CS_TILE; // tiles with all 256 records
-    const uint64_t n_units = (uint64_t)gridDim.x * ST_WAVES, unit = (uint64_t)blockIdx.x * ST_WAVES + wave;
-    const uint64_t per = (n_wt + n_units - 1) / n_units;
-    const uint64_t t_begin = per * unit < n_wt ? per * unit : n_wt;
-    const uint64_t t_end = t_begin + per < n_wt ? t_begin + per : n_wt;
     const uint32_t maxspan = *st.batch_span;
 
     uint32_t hot_base = 0;  // depth of the hot window's first bin (wave-uniform)
@@ -578,36 +577,56 @@ __global__ __launch_bounds__(ST_THREADS, ST_MIN_BLOCKS) void k_cov_stream(Device
         __builtin_amdgcn_wave_barrier();
     };
 
-    // ---- full tiles: the next tile's inputs are in flight while this one is processed (two tiles ahead was
-    // measured: no faster, and the extra registers spill)
-    uint64_t t = t_begin;
-    const uint64_t t_full_end = t_end < n_full ? t_end : n_full;
-    if (t < t_full_end) {
-        StTileIn cur = load_full(t);
-        while (t < t_full_end) {
-            const uint64_t tn = t + 1;
-            const StTileIn nxt = load_full(tn < n_full ? tn : t); // past the end: a re-read
-            process(cur, t);
-            cur = nxt;
-            t = tn;
+    // ---- runs of run_len consecutive tiles.  Alone on the device the whole grid is resident: one run per wave, its even share.
+    // Beside k_gc the runs (CS_RUN tiles, fewer in a small batch) are handed out through one counter, so that a wave's share does
+    // not depend on how many blocks of the grid are resident: few while k_gc runs, more once its blocks retire, and the tiles of a
+    // real genome differ in cost by far more than the waves in speed.  The first tile of a run finds no list and walks back; a
+    // wave that happens to take the run behind its own goes on with its list.  Nothing here waits for another wave.
+    auto tiles_from = [&](uint64_t t_begin) {
+        const uint64_t t_end = t_begin + run_len < n_wt ? t_begin + run_len : n_wt;
+        // full tiles: the next tile's inputs are in flight while this one is processed (two tiles ahead was measured, alone and
+        // beside k_gc: no faster either way, and the extra registers spill or cost the third wave per SIMD -- at k_cov_stream_corun)
+        uint64_t t = t_begin;
+        const uint64_t t_full_end = t_end < n_full ? t_end : n_full;
+        if (t < t_full_end) {
+            StTileIn cur = load_full(t);
+            while (t < t_full_end) {
+                const uint64_t tn = t + 1;
+                const StTileIn nxt = load_full(tn < n_full ? tn : t); // past the end: a re-read
+                process(cur, t);
+                cur = nxt;
+                t = tn;
+            }
         }
-    }
-    if (n_full < n_wt && t_begin <= n_full && n_full < t_end) { // the partial last tile: element by element, never streamable
-        const uint64_t base = n_full * CS_TILE, r0 = base + (uint64_t)lane * 4;
-        int32_t p[4];
-        uint32_t c[4];
+        if (n_full < n_wt && t_begin <= n_full && n_full < t_end) { // the partial last tile: element by element, never streamable
+            const uint64_t base = n_full * CS_TILE, r0 = base + (uint64_t)lane * 4;
+            int32_t p[4];
+            uint32_t c[4];
 #pragma unroll
-        for (uint32_t j = 0; j < 4; j++) {
-            const bool ok = r0 + j < b.n;
-            p[j] = ok ? b.pos[r0 + j] : -1;
-            c[j] = ok ? st.cov_end[r0 + j] : 0u;
+            for (uint32_t j = 0; j < 4; j++) {
+                const bool ok = r0 + j < b.n;
+                p[j] = ok ? b.pos[r0 + j] : -1;
+                c[j] = ok ? st.cov_end[r0 + j] : 0u;
+            }
+            StTileIn in;
+            in.p = make_int4(p[0], p[1], p[2], p[3]);
+            in.c = make_uint4(c[0], c[1], c[2], c[3]);
+            in.rf_t = in.rf_n = b.ref_id[base];
+            in.ps_t = in.ps_n = b.pos[base];
+            process(in, n_full);
         }
-        StTileIn in;
-        in.p = make_int4(p[0], p[1], p[2], p[3]);
-        in.c = make_uint4(c[0], c[1], c[2], c[3]);
-        in.rf_t = in.rf_n = b.ref_id[base];
-        in.ps_t = in.ps_n = b.pos[base];
-        process(in, n_full);
+    };
+    if constexpr (CORUN) {
+        for (;;) {
+            uint32_t run = 0;
+            if (lane == 0) run = atomicAdd(a.run_next, 1u);
+            const uint64_t t_begin = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)run) * run_len;
+            if (t_begin >= n_wt) break;
+            tiles_from(t_begin);
+        }
+    } else {
+        const uint64_t t_begin = ((uint64_t)blockIdx.x * ST_WAVES + wave) * run_len;
+        if (t_begin < n_wt) tiles_from(t_begin);
     }
     flush_hist();
     flush_bin();
@@ -623,25 +642,56 @@ __global__ __launch_bounds__(ST_THREADS, ST_MIN_BLOCKS) void k_cov_stream(Device
     }
 }
 
-hipError_t launch_cov_stream(const LaunchInfo &li, const DeviceState &st, const DeviceBatch &b, const CovStreamArgs &a,
-                             hipStream_t s) {
+__global__ __launch_bounds__(ST_THREADS, 4) void k_cov_stream(DeviceState st, DeviceBatch b, CovStreamArgs a, uint32_t run_len) {
+    cov_stream_body<false>(st, b, a, run_len);
+}
+// Beside k_gc: three waves per SIMD at most instead of four, which gives the compiler up to 168 registers; as built it takes 160 and
+// no scratch (the serial kernel: 128 and 40 bytes).  Two such waves fit beside four of k_gc (2 x 160 + 4 x 40 = 480 of a SIMD's 512
+// registers; 2 x 160 + 3 x 48 = 464 with the k_gc variants that are allocated 48); the third block of a CU becomes resident when
+// k_gc's blocks retire.  Measured beside k_gc and not kept (profiles/r07_corun_ab.txt, DESIGN_HISTORY A.9): two waves per SIMD with
+// up to 256 registers (174 used: no faster, and the whole-genome pass loses its third block: 11.3-12.0 ms against 10.45); four waves
+// per SIMD in 128 registers (196 bytes of scratch, 2.8-3.0 ms); the inputs of two tiles in flight in named slots instead of `cur =
+// nxt` (14 more registers, 1.56-1.76 ms against 1.44-1.62 at equal settings).
+__global__ __launch_bounds__(ST_THREADS, 3) void k_cov_stream_corun(DeviceState st, DeviceBatch b, CovStreamArgs a, uint32_t run_len) {
+    cov_stream_body<true>(st, b, a, run_len);
+}
+
+hipError_t launch_cov_plan(const DeviceState &st, const DeviceBatch &b, const CovStreamArgs &a, hipStream_t s) {
     if (!b.n) return hipSuccess;
     const uint64_t n_wt = (b.n + CS_TILE - 1) / CS_TILE;
     hipLaunchKernelGGL(k_cov_plan_tiles, dim3((uint32_t)((n_wt + 255) / 256)), dim3(256), 0, s, st, b, a);
     hipLaunchKernelGGL(k_cov_plan_refs, dim3((st.n_refs + 255) / 256), dim3(256), 0, s, st, a);
+    return hipGetLastError();
+}
+
+// blocks per CU launched beside k_gc (kernels.hip GC_CORUN_BLOCKS): what is resident once k_gc has gone; two of them beside it
+constexpr uint32_t CS_CORUN_BLOCKS = 3;
+hipError_t launch_cov_stream(const LaunchInfo &li, const DeviceState &st, const DeviceBatch &b, const CovStreamArgs &a,
+                             bool corun, hipStream_t s) {
+    if (!b.n) return hipSuccess;
+    const uint64_t n_wt = (b.n + CS_TILE - 1) / CS_TILE;
     const size_t lds = (size_t)ST_WAVES * (ST_W + st_hist_words(a.cov_cap) + ST_HOT + ST_LIST) * sizeof(uint32_t);
     static bool attr = false;
     if (!attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_cov_stream),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
-        if (e != hipSuccess) return e;
+        for (const void *k : {reinterpret_cast<const void *>(k_cov_stream), reinterpret_cast<const void *>(k_cov_stream_corun)}) {
+            hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
+            if (e != hipSuccess) return e;
+        }
         attr = true;
     }
-    uint64_t g = (n_wt + ST_WAVES - 1) / ST_WAVES;
     const uint64_t per_cu = (160 * 1024 - 1024) / lds; // blocks that fit the 160 KB of LDS of one CU
-    const uint64_t cap = (uint64_t)li.n_cu * (per_cu < 1 ? 1 : per_cu > 6 ? 6 : per_cu);
+    const uint64_t fit = per_cu < 1 ? 1 : per_cu > 6 ? 6 : per_cu;
+    const uint64_t cap = (uint64_t)li.n_cu * (corun && fit > CS_CORUN_BLOCKS ? CS_CORUN_BLOCKS : fit);
+    uint64_t g = (n_wt + ST_WAVES - 1) / ST_WAVES;
     if (g > cap) g = cap;
-    hipLaunchKernelGGL(k_cov_stream, dim3((uint32_t)g), dim3(ST_THREADS), lds, s, st, b, a);
+    // a wave's even share of the tiles: alone that is its one run; beside k_gc a run is at most CS_RUN tiles (fewer in a batch too
+    // small to give every wave that many), and the grid has no more waves than there are runs
+    const uint64_t share = (n_wt + g * ST_WAVES - 1) / (g * ST_WAVES);
+    const uint32_t run_len = (uint32_t)(corun && share > CS_RUN ? CS_RUN : share);
+    const uint64_t n_runs = (n_wt + run_len - 1) / run_len;
+    if (g > (n_runs + ST_WAVES - 1) / ST_WAVES) g = (n_runs + ST_WAVES - 1) / ST_WAVES;
+    if (corun) hipLaunchKernelGGL(k_cov_stream_corun, dim3((uint32_t)g), dim3(ST_THREADS), lds, s, st, b, a, run_len);
+    else hipLaunchKernelGGL(k_cov_stream, dim3((uint32_t)g), dim3(ST_THREADS), lds, s, st, b, a, run_len);
     return hipGetLastError();
 }
 

@@ -30,6 +30,10 @@
 // (another stream, persistent waves that keep the scalar and vector issue ports busy): their waves ask for the highest
 // issue priority, or a latency-bound kernel like the record-chain walk runs ten times slower beside the decoders than alone.
 #define NGSQ_FOREGROUND_WAVE() __builtin_amdgcn_s_setprio(3)
+// k_gc while k_cov_stream runs beside it (context.cpp launch_all): one step below.  Issue is arbitrated by priority, then age, and
+// k_gc's waves are the older ones: at equal priority the instruction-bound k_cov_stream took 2.08 ms beside it instead of 0.71
+// alone and the pair was no faster than one kernel after the other; one step below, k_gc waits for HBM most of the time anyway.
+#define NGSQ_BESIDE_FOREGROUND_WAVE() __builtin_amdgcn_s_setprio(2)
 
 namespace ngsq {
 
@@ -163,12 +167,17 @@ struct CovStreamArgs {
     const uint64_t *bin_off;
     uint32_t bin_size, cov_cap, head_guard;
     uint32_t *span_next;             // the word the NEXT batch collects its largest span in (zeroed by k_cov_plan_refs)
+    uint32_t *run_next;              // [1] next run of CS_RUN tiles nobody has taken yet (zeroed by k_cov_plan_refs)
 };
+constexpr uint32_t CS_RUN = 48;            // consecutive tiles a wave of k_cov_stream takes at a time
+// the two plan kernels of a batch (microseconds), then the pass itself.  corun: the launch shares every CU with a k_gc
+// launched with the same flag on another stream -- both are persistent, so their grids fix each one's share
+hipError_t launch_cov_plan(const DeviceState &st, const DeviceBatch &b, const CovStreamArgs &a, hipStream_t s);
 hipError_t launch_cov_stream(const LaunchInfo &li, const DeviceState &st, const DeviceBatch &b, const CovStreamArgs &a,
-                             hipStream_t s);
+                             bool corun, hipStream_t s);
 // GC Content (gc_content.rs:38-100)
 hipError_t launch_gc(const LaunchInfo &li, const DeviceState &st, const DeviceBatch &b,
-                     uint64_t seq_bytes, hipStream_t s);
+                     uint64_t seq_bytes, bool corun, hipStream_t s);
 // Quality Score (quality_scores.rs:37-49)
 hipError_t launch_qual(const LaunchInfo &li, const DeviceState &st, const DeviceBatch &b,
                        hipStream_t s);

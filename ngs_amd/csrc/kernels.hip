@@ -82,8 +82,9 @@ __device__ __forceinline__ void gc_dword(uint32_t x, uint32_t mask, uint32_t &gc
 // iteration ahead as well -- a two-stage pipeline, 66-75 registers -- measured 1.62 on the offsets layout and 2.65 on
 // fixed-pitch rows: not kept.)
 template <bool OFFS, bool RID>
-__global__ __launch_bounds__(256) void k_gc(DeviceState st, DeviceBatch b, uint64_t seq_bytes) {
-    NGSQ_FOREGROUND_WAVE();
+__global__ __launch_bounds__(256) void k_gc(DeviceState st, DeviceBatch b, uint64_t seq_bytes, uint32_t corun) {
+    if (corun) NGSQ_BESIDE_FOREGROUND_WAVE();
+    else NGSQ_FOREGROUND_WAVE();
     __shared__ uint32_t s_hist[NGSQ_GC_BINS];
     __shared__ u64 s_acc[6];
     if (threadIdx.x < NGSQ_GC_BINS) s_hist[threadIdx.x] = 0;
@@ -233,14 +234,21 @@ static inline uint32_t grid_for(uint64_t n, uint32_t per_block, uint32_t max_blo
     return (uint32_t)g;
 }
 
-hipError_t launch_gc(const LaunchInfo &li, const DeviceState &st, const DeviceBatch &b, uint64_t seq_bytes,
+// corun: k_cov_stream runs beside this launch (context.cpp launch_all).  Both grids are persistent, so they -- not the
+// dispatcher -- say how a CU is shared: a full grid of eight blocks kept that kernel waiting for wave slots.  Four
+// blocks of four waves leave two waves per SIMD of k_cov_stream_corun their registers (160 each as built: 4 x 40 + 2 x 160 = 480 of
+// 512); the variants with offsets or record identities hold 42 registers, 48 as allocated: three blocks (3 x 48 + 2 x 160 = 464).  Between three and six blocks
+// k_gc's time beside k_cov_stream did not depend on the number (profiles/r07_corun_ab.txt).
+constexpr uint32_t GC_BLOCKS = 8, GC_CORUN_BLOCKS = 4, GC_CORUN_BLOCKS_WIDE = 3;
+hipError_t launch_gc(const LaunchInfo &li, const DeviceState &st, const DeviceBatch &b, uint64_t seq_bytes, bool corun,
                      hipStream_t s) {
     if (!b.n) return hipSuccess;
-    const uint32_t grid = grid_for(b.n, 256 * 4, li.n_cu * 8);
-    if (b.seq_off && b.record_id) hipLaunchKernelGGL((k_gc<true, true>), dim3(grid), dim3(256), 0, s, st, b, seq_bytes);
-    else if (b.seq_off) hipLaunchKernelGGL((k_gc<true, false>), dim3(grid), dim3(256), 0, s, st, b, seq_bytes);
-    else if (b.record_id) hipLaunchKernelGGL((k_gc<false, true>), dim3(grid), dim3(256), 0, s, st, b, seq_bytes);
-    else hipLaunchKernelGGL((k_gc<false, false>), dim3(grid), dim3(256), 0, s, st, b, seq_bytes);
+    const uint32_t per_cu = !corun ? GC_BLOCKS : b.seq_off || b.record_id ? GC_CORUN_BLOCKS_WIDE : GC_CORUN_BLOCKS;
+    const uint32_t grid = grid_for(b.n, 256 * 4, li.n_cu * per_cu);
+    if (b.seq_off && b.record_id) hipLaunchKernelGGL((k_gc<true, true>), dim3(grid), dim3(256), 0, s, st, b, seq_bytes, corun ? 1u : 0u);
+    else if (b.seq_off) hipLaunchKernelGGL((k_gc<true, false>), dim3(grid), dim3(256), 0, s, st, b, seq_bytes, corun ? 1u : 0u);
+    else if (b.record_id) hipLaunchKernelGGL((k_gc<false, true>), dim3(grid), dim3(256), 0, s, st, b, seq_bytes, corun ? 1u : 0u);
+    else hipLaunchKernelGGL((k_gc<false, false>), dim3(grid), dim3(256), 0, s, st, b, seq_bytes, corun ? 1u : 0u);
     return hipGetLastError();
 }
 
