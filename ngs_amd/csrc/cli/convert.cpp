@@ -1,7 +1,8 @@
 // convert.cpp -- `ngs convert` (src/convert/command.rs:26-172, src/convert/bam.rs:24-70): BAM to SAM, the
 // text formatted on the GPU by ngsq_bam_write_sam (include/ngsq_sam.h); and, behind the additive `--gzip device`, SAM to BAM
 // (src/convert/sam.rs:26-90): the text parsed and the BGZF written on the GPU by ngsq_sam_write_bam
-// (include/ngsq_samtext.h).  Without the flag every command line answers as a build without that direction.
+// (include/ngsq_samtext.h); with the additive `--sort coordinate` beside it the records are sorted there too
+// (ngsq_sam_write_sorted_bam).  Without the flags every command line answers as a build without that direction.
 #include <fcntl.h>
 
 #include <algorithm>
@@ -17,6 +18,7 @@ struct ConvertArgs {
     std::vector<std::string> pos;
     bool has_n = false, has_fasta = false; // (-r and -c take no part in BAM to SAM, as in the reference)
     bool gzip_device = false;              // --gzip device: SAM to BAM is converted, its BGZF written on the GPU
+    bool sort_coordinate = false;          // --sort coordinate: ... and its records sorted there
     unsigned long long n = 0;
     int device = 0;
 };
@@ -44,7 +46,10 @@ bool parse_args(int argc, char **argv, int at, ConvertArgs *a) {
                     "          GPU the SAM text is formatted on (additive, this build) [default: 0]\n"
                     "      --gzip <WHERE>\n"
                     "          Where BGZF output is compressed (additive, this build): `device` converts SAM to BAM on the GPU;\n"
-                    "          `host` changes nothing [default: host] [possible values: host, device]\n\n"
+                    "          `host` changes nothing [default: host] [possible values: host, device]\n"
+                    "      --sort <ORDER>\n"
+                    "          Order of the records of a BAM written with --gzip device (additive, this build): `coordinate` sorts them\n"
+                    "          on the GPU, unplaced records last, and writes SO:coordinate [default: none] [possible values: none, coordinate]\n\n"
                     "This build converts BAM to SAM, and with --gzip device SAM to BAM: the text is parsed and the BGZF blocks are\n"
                     "written on the GPU, whose encoder has one setting (-c is checked and takes no part).\n");
             return false;
@@ -70,6 +75,11 @@ bool parse_args(int argc, char **argv, int at, ConvertArgs *a) {
             if (v == "host") a->gzip_device = false;
             else if (v == "device") a->gzip_device = true;
             else bail("invalid value '" + v + "' for '--gzip <WHERE>' [possible values: host, device]");
+        } else if (s == "--sort") {
+            const std::string v = val("--sort <ORDER>");
+            if (v == "none") a->sort_coordinate = false;
+            else if (v == "coordinate") a->sort_coordinate = true;
+            else bail("invalid value '" + v + "' for '--sort <ORDER>' [possible values: none, coordinate]");
         } else if (!s.empty() && s[0] == '-' && s != "-") bail("unexpected argument '" + s + "' found");
         else a->pos.push_back(s);
     }
@@ -95,14 +105,25 @@ int sam_to_bam(const ConvertArgs &a, const std::string &from, const std::string 
     }
     const uint64_t max_records = a.has_n ? std::max<unsigned long long>(a.n, 1) : 0;
     ngsq_samtext_report rep{};
-    const int rc = ngsq_sam_write_bam(ctx, from.c_str(), fd, max_records, 0, &rep);
+    ngsq_samsort_report srep{};
+    const int rc = a.sort_coordinate ? ngsq_sam_write_sorted_bam(ctx, from.c_str(), fd, max_records, 0, 0, 0, &srep)
+                                     : ngsq_sam_write_bam(ctx, from.c_str(), fd, max_records, 0, &rep);
     const std::string msg = rc ? ngsq_last_error(ctx) : "";
     const int close_rc = close(fd), close_errno = errno;
     ngsq_destroy(ctx);
     if (rc) bail(msg);
     if (close_rc) bail(std::string("writing BAM record: ") + strerror(close_errno) + " (os error " + std::to_string(close_errno) + ")");
-    for (uint64_t m = 1; m <= rep.records / 1000000; m++) logf(2, "  [*] Processed %s records.", with_commas(m * 1000000).c_str());
-    if (g_level >= 3)
+    const uint64_t written = a.sort_coordinate ? srep.records : rep.records;
+    for (uint64_t m = 1; m <= written / 1000000; m++) logf(2, "  [*] Processed %s records.", with_commas(m * 1000000).c_str());
+    if (g_level >= 3 && a.sort_coordinate)
+        fprintf(stderr, "[ngs] convert: %llu records in %llu chunks sorted in %u of 8 passes, %llu header + %llu text bytes -> %llu BAM bytes in %llu pieces, "
+                        "%llu blocks (%llu stored), %llu compressed; read %.1f ms, up %.1f ms, parse %.1f ms, sort %.1f ms, gather %.1f ms, deflate %.1f ms, "
+                        "down %.1f ms, write %.1f ms, total %.1f ms\n",
+                (unsigned long long)srep.records, (unsigned long long)srep.chunks, srep.passes_run, (unsigned long long)srep.header_bytes,
+                (unsigned long long)srep.text_bytes, (unsigned long long)srep.bam_bytes, (unsigned long long)srep.pieces, (unsigned long long)srep.blocks,
+                (unsigned long long)srep.stored_blocks, (unsigned long long)srep.compressed_bytes, srep.read_ms, srep.h2d_ms, srep.parse_ms, srep.sort_ms,
+                srep.gather_ms, srep.deflate_ms, srep.d2h_ms, srep.write_ms, srep.total_ms);
+    else if (g_level >= 3)
         fprintf(stderr, "[ngs] convert: %llu records in %llu chunks, %llu header + %llu text bytes -> %llu BAM bytes in %llu blocks (%llu stored), "
                         "%llu compressed; read %.1f ms, up %.1f ms, parse %.1f ms, deflate %.1f ms, down %.1f ms, write %.1f ms, total %.1f ms\n",
                 (unsigned long long)rep.records, (unsigned long long)rep.chunks, (unsigned long long)rep.header_bytes,

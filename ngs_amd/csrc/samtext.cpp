@@ -7,158 +7,11 @@
 // writes it.  Per chunk the host reads four words: lines, record bytes, error word, compressed bytes.
 #include "../../include/ngsq_samtext.h"
 
-#include <fcntl.h>
-
-#include <cstdarg>
-#include <unordered_set>
-
-#include "device_out.h"
-#include "samtext_kernels.h"
+#include "samtext_host.h"
 
 using namespace ngsq;
 
 namespace {
-
-constexpr uint64_t ST_CHUNK_DEFAULT = (uint64_t)64 << 20, ST_CHUNK_MAX = (uint64_t)1 << 30; // (a line's record stays under 2^31 bytes)
-constexpr const char *OPEN_CTX = "opening SAM input file: ";
-
-int sfail(ngsq_ctx *c, int code, const char *fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (c) c->err = buf;
-    return code;
-}
-
-const char *samtext_error_text(uint32_t code) {
-    switch (code) {
-    case ST_E_FIELDS: return "fewer than 11 fields";
-    case ST_E_QNAME_EMPTY: return "empty read name";
-    case ST_E_QNAME_LONG: return "read name longer than 254 bytes";
-    case ST_E_FLAG: return "invalid FLAG";
-    case ST_E_RNAME: return "reference sequence name not in the header";
-    case ST_E_POS: return "invalid POS";
-    case ST_E_MAPQ: return "invalid MAPQ";
-    case ST_E_CIGAR_DIGITS: return "CIGAR operation without a length";
-    case ST_E_CIGAR_OP: return "invalid CIGAR operation";
-    case ST_E_CIGAR_LEN: return "CIGAR operation length of 2^28 or more";
-    case ST_E_RNEXT: return "mate reference sequence name not in the header";
-    case ST_E_PNEXT: return "invalid PNEXT";
-    case ST_E_TLEN: return "invalid TLEN";
-    case ST_E_SEQ: return "invalid SEQ base";
-    case ST_E_QUAL_NO_SEQ: return "QUAL without SEQ";
-    case ST_E_QUAL_LEN: return "QUAL length differs from SEQ length";
-    case ST_E_QUAL_CHAR: return "QUAL byte outside 33..126";
-    case ST_E_TAG_FORM: return "tag not of the form TG:T:V";
-    case ST_E_TAG_TYPE: return "invalid tag value type";
-    case ST_E_B_SUB: return "invalid B array subtype";
-    case ST_E_NUMBER: return "malformed number";
-    case ST_E_HEX: return "invalid H value";
-    case ST_E_FLOAT_LONG: return "float text longer than 48 characters";
-    case ST_E_TOO_LARGE: return "record larger than 2^31 bytes";
-    default: return "invalid record";
-    }
-}
-
-struct Fd {
-    int fd = -1;
-    ~Fd() {
-        if (fd >= 0) close(fd);
-    }
-};
-
-struct SamHeader {
-    std::string text;               // the leading '@' lines, unchanged
-    std::vector<std::string> names; // @SQ SN, file order
-    std::vector<uint32_t> lens;     // @SQ LN
-    uint64_t body_at = 0;           // file offset of the first record line
-};
-
-// pread until n bytes or the end of the file; the bytes read, or -errno
-ssize_t pread_full(int fd, char *p, size_t n, uint64_t at) {
-    size_t got = 0;
-    while (got < n) {
-        const ssize_t r = pread(fd, p + got, n - got, (off_t)(at + got));
-        if (r < 0) {
-            if (errno == EINTR) continue;
-            return -errno;
-        }
-        if (r == 0) break;
-        got += (size_t)r;
-    }
-    return (ssize_t)got;
-}
-
-// The header of the SAM file fd; "" or why it is refused (without the context).
-std::string read_header(int fd, SamHeader *h) {
-    std::vector<char> buf((size_t)1 << 20);
-    uint64_t at = 0;
-    bool line_start = true, done = false;
-    while (!done) {
-        const ssize_t n = pread_full(fd, buf.data(), buf.size(), at);
-        if (n < 0) return std::string(strerror((int)-n)) + " (os error " + std::to_string(-n) + ")";
-        if (n == 0) break;
-        ssize_t i = 0;
-        for (; i < n; i++) {
-            if (line_start && buf[(size_t)i] != '@') {
-                done = true;
-                break;
-            }
-            line_start = buf[(size_t)i] == '\n';
-            h->text.push_back(buf[(size_t)i]);
-        }
-        at += (uint64_t)i;
-    }
-    h->body_at = at;
-    if (h->text.size() > 0x7FFFFFFFull) return "header text longer than 2^31 - 1 bytes";
-    // the reference list: SN and LN of the @SQ lines (the text itself goes into the file as it is)
-    std::unordered_set<std::string> seen;
-    for (size_t a = 0; a < h->text.size();) {
-        size_t e = h->text.find('\n', a);
-        if (e == std::string::npos) e = h->text.size();
-        if (e - a >= 4 && h->text.compare(a, 4, "@SQ\t") == 0) {
-            std::string sn, ln;
-            bool has_sn = false, has_ln = false;
-            for (size_t f = a + 4; f <= e;) {
-                size_t fe = h->text.find('\t', f);
-                if (fe == std::string::npos || fe > e) fe = e;
-                if (fe - f >= 3 && h->text.compare(f, 3, "SN:") == 0 && !has_sn) sn = h->text.substr(f + 3, fe - f - 3), has_sn = true;
-                if (fe - f >= 3 && h->text.compare(f, 3, "LN:") == 0 && !has_ln) ln = h->text.substr(f + 3, fe - f - 3), has_ln = true;
-                f = fe + 1;
-            }
-            const std::string line_no = std::to_string(h->names.size() + 1);
-            if (!has_sn || sn.empty()) return "@SQ line " + line_no + " has no SN";
-            if (!has_ln) return "@SQ line " + line_no + " (" + sn + ") has no LN";
-            uint64_t v = 0;
-            bool digits = !ln.empty();
-            for (char ch : ln) {
-                if (ch < '0' || ch > '9') digits = false;
-                else if (v < ((uint64_t)1 << 40)) v = v * 10 + (uint64_t)(ch - '0');
-            }
-            if (!digits || v < 1 || v > 0x7FFFFFFFull) return "@SQ line " + line_no + " (" + sn + "): LN " + ln + " is outside 1..2147483647";
-            if (!seen.insert(sn).second) return "@SQ line " + line_no + ": the sequence name " + sn + " stands in more than one @SQ line";
-            h->names.push_back(sn);
-            h->lens.push_back((uint32_t)v);
-        }
-        a = e + 1;
-    }
-    if (h->names.size() > 0x7FFFFFFFull) return "more than 2^31 - 1 @SQ lines";
-    return "";
-}
-
-void put32(std::string &s, uint32_t v) {
-    char b[4] = {(char)v, (char)(v >> 8), (char)(v >> 16), (char)(v >> 24)};
-    s.append(b, 4);
-}
-
-struct PinnedText {
-    char *p = nullptr;
-    ~PinnedText() {
-        if (p) (void)hipHostFree(p);
-    }
-};
 
 enum Ev { EV_UP0 = 0, EV_UP1, EV_H0, EV_H1, EV_P0, EV_P1, EV_W0, EV_W1, EV_Z1, EV_N };
 
@@ -175,7 +28,7 @@ int ngsq_sam_parse_f32(const char *text, uint32_t len, uint32_t *bits) {
 
 int ngsq_sam_check_header(const char *sam_path, uint32_t *n_refs, char *why, size_t why_cap) {
     auto say = [&](const std::string &m) {
-        if (why && why_cap) snprintf(why, why_cap, "%s%s", OPEN_CTX, m.c_str());
+        if (why && why_cap) snprintf(why, why_cap, "%s%s", ST_OPEN_CTX, m.c_str());
         return NGSQ_ERR_INVALID_ARGUMENT;
     };
     if (why && why_cap) why[0] = 0;
@@ -203,42 +56,15 @@ int ngsq_sam_write_bam(ngsq_ctx *c, const char *sam_path, int fd, uint64_t max_r
     in.fd = open(sam_path, O_RDONLY | O_CLOEXEC);
     if (in.fd < 0) {
         const int e = errno;
-        return sfail(c, NGSQ_ERR_INVALID_ARGUMENT, "%s%s (os error %d)", OPEN_CTX, strerror(e), e);
+        return sfail(c, NGSQ_ERR_INVALID_ARGUMENT, "%s%s (os error %d)", ST_OPEN_CTX, strerror(e), e);
     }
     SamHeader H;
     {
         const std::string m = read_header(in.fd, &H);
-        if (!m.empty()) return sfail(c, NGSQ_ERR_INVALID_ARGUMENT, "%s%s", OPEN_CTX, m.c_str());
+        if (!m.empty()) return sfail(c, NGSQ_ERR_INVALID_ARGUMENT, "%s%s", ST_OPEN_CTX, m.c_str());
     }
-    const uint32_t n_refs = (uint32_t)H.names.size();
-    // the header stream: magic, l_text, text, n_ref, names and lengths (SAM/BAM specification 4.2)
-    std::string hs("BAM\1", 4);
-    put32(hs, (uint32_t)H.text.size());
-    hs += H.text;
-    put32(hs, n_refs);
-    for (uint32_t r = 0; r < n_refs; r++) {
-        put32(hs, (uint32_t)H.names[r].size() + 1);
-        hs += H.names[r];
-        hs.push_back('\0');
-        put32(hs, H.lens[r]);
-    }
-    // the reference names for the device: [bad word | name_off[n_refs + 1] | table[slots] | names]
-    uint32_t slots = 1;
-    while (slots < 2ull * n_refs) slots <<= 1;
-    std::vector<uint64_t> setup(1 + n_refs + 1 + (slots + 1) / 2, 0);
-    std::string names;
-    setup[0] = ~0ull;
-    {
-        uint32_t *table = reinterpret_cast<uint32_t *>(setup.data() + 1 + n_refs + 1);
-        for (uint32_t r = 0; r < n_refs; r++) {
-            setup[1 + r] = names.size();
-            names += H.names[r];
-            uint32_t s = samtext_name_hash(reinterpret_cast<const uint8_t *>(H.names[r].data()), H.names[r].size()) & (slots - 1);
-            while (table[s]) s = (s + 1) & (slots - 1);
-            table[s] = r + 1;
-        }
-        setup[1 + n_refs] = names.size();
-    }
+    const std::string hs = header_stream(H.text, H);
+    const RefTable rt(H);
 
     // ---- the device side; every HIP error leaves through `rc`, so that the writer is stopped either way
 #define SHIP(expr)                                                                                  \
@@ -253,53 +79,23 @@ int ngsq_sam_write_bam(ngsq_ctx *c, const char *sam_path, int fd, uint64_t max_r
     BgzfEncoder enc; // d_rec's bytes become the blocks of a job
     JobSlots zslots; // of the encoder's blocks (d_text alternates with the chunks, apart from them)
     MappedBuf hw;
-    PinnedText pin[2];
+    TextChunks text;
     HipEvents<EV_N> ev;
     DeviceWriter w;
     StreamDrain drain{st}, drain_up{nullptr, true}; // (behind the arrays: they run first)
-    const size_t pin_bytes = (size_t)chunk_bytes + 2 + ST_TEXT_SLACK;
     uint64_t records = 0, text_bytes = 0, bam_bytes = 0, chunks = 0, bad = ~0ull;
-    double read_ms = 0, h2d_ms = 0, parse_ms = 0, deflate_ms = 0;
-    uint64_t file_at = H.body_at;
-    size_t carry = 0; // bytes of the line the last chunk ended inside, at the front of the next buffer
-    bool eof = false;
-    std::string long_line; // the refusal of a line that does not fit a chunk
-
-    // the next chunk into pin[slot]: *len bytes that end on a newline (0: the file has ended)
+    double h2d_ms = 0, parse_ms = 0, deflate_ms = 0;
+    // the next chunk into the text's buffer `slot`: *len bytes that end on a newline (0: the file has ended)
     auto fill = [&](uint32_t slot, uint64_t *len) -> int {
-        const double t0 = now_ms();
-        char *buf = pin[slot].p;
-        size_t have = carry;
-        *len = 0;
-        if (!eof && have < chunk_bytes + 1) {
-            const ssize_t r = pread_full(in.fd, buf + have, (size_t)chunk_bytes + 1 - have, file_at);
-            if (r < 0) return sfail(c, NGSQ_ERR_INVALID_ARGUMENT, "reading SAM record: %s (os error %d)", strerror((int)-r), (int)-r);
-            if ((size_t)r < chunk_bytes + 1 - have) eof = true;
-            have += (size_t)r;
-            file_at += (uint64_t)r;
-        }
-        read_ms += now_ms() - t0;
-        if (!have) return NGSQ_OK;
-        const char *nl = static_cast<const char *>(memrchr(buf, '\n', have));
-        size_t cut = nl ? (size_t)(nl - buf) + 1 : 0;
-        if (!nl && have > chunk_bytes) {
-            long_line = "line longer than " + std::to_string(chunk_bytes) + " bytes";
-            return NGSQ_OK;
-        }
-        if (eof && cut < have) { // a last line without its newline is a line
-            buf[have++] = '\n';
-            cut = have;
-        }
-        carry = have - cut;
-        *len = cut;
+        if (const int e = text.fill(slot, len)) return sfail(c, NGSQ_ERR_INVALID_ARGUMENT, "reading SAM record: %s (os error %d)", strerror(e), e);
         return NGSQ_OK;
     };
     // pin[slot][0, len) to d_text[slot] on the copy stream; the carry moves to the other buffer first (the copy only reads)
     auto upload = [&](uint32_t slot, uint64_t len) -> int {
-        if (carry) memcpy(pin[slot ^ 1].p, pin[slot].p + len, carry);
+        text.move_carry(slot, len);
         SHIP(d_text[slot].reserve(len + ST_TEXT_SLACK));
         SHIP(hipEventRecord(ev.e[EV_H0], up));
-        SHIP(hipMemcpyAsync(d_text[slot].p, pin[slot].p, len, hipMemcpyHostToDevice, up));
+        SHIP(hipMemcpyAsync(d_text[slot].p, text.pin[slot].p, len, hipMemcpyHostToDevice, up));
         SHIP(hipEventRecord(ev.e[EV_H1], up));
         SHIP(hipEventRecord(ev.e[EV_UP0 + slot], up));
         return NGSQ_OK;
@@ -329,22 +125,16 @@ int ngsq_sam_write_bam(ngsq_ctx *c, const char *sam_path, int fd, uint64_t max_r
         SHIP(hipSetDevice(c->device));
         SHIP(pool_stream_get(false, &up));
         drain_up.s = up;
-        SHIP(d_setup.reserve(setup.size() + (names.size() + 7) / 8));
-        SHIP(hipMemcpyAsync(d_setup.p, setup.data(), setup.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        if (!names.empty()) SHIP(hipMemcpyAsync(d_setup.p + setup.size(), names.data(), names.size(), hipMemcpyHostToDevice, st));
-        SHIP(hipStreamSynchronize(st)); // (setup and names are this function's)
-        unsigned long long *const d_bad = reinterpret_cast<unsigned long long *>(d_setup.p);
-        const SamTextRefs refs{reinterpret_cast<const uint32_t *>(d_setup.p + 1 + n_refs + 1), d_setup.p + 1, reinterpret_cast<const uint8_t *>(d_setup.p + setup.size()),
-                               slots, n_refs};
+        SHIP(d_setup.reserve(rt.device_words()));
+        SHIP(rt.upload(d_setup.p, st));
+        SHIP(hipStreamSynchronize(st));
+        unsigned long long *const d_bad = rt.bad(d_setup.p);
+        const SamTextRefs refs = rt.refs(d_setup.p);
         SHIP(hw.reserve(HW_WORDS * sizeof(unsigned long long)));
         memset(hw.h, 0, HW_WORDS * sizeof(unsigned long long));
         unsigned long long *const hdev = static_cast<unsigned long long *>(hw.dev);
         const unsigned long long *const h = static_cast<const unsigned long long *>(hw.h);
-        for (int k = 0; k < 2; k++) {
-            void *p = nullptr;
-            SHIP(hipHostMalloc(&p, pin_bytes, hipHostMallocDefault));
-            pin[k].p = static_cast<char *>(p);
-        }
+        SHIP(text.start(in.fd, chunk_bytes, H.body_at));
         enc.h = h + HW_DEFLATE;
         enc.hdev = hdev + HW_DEFLATE;
         for (int k = 0; k < EV_N; k++) {
@@ -439,8 +229,8 @@ int ngsq_sam_write_bam(ngsq_ctx *c, const char *sam_path, int fd, uint64_t max_r
     if (rc == NGSQ_OK && bad != ~0ull)
         rc = sfail(c, NGSQ_ERR_MALFORMED_RECORD, "reading SAM record: record %llu: %s", (unsigned long long)(bad >> ST_ERR_BITS),
                    samtext_error_text((uint32_t)(bad & ((1u << ST_ERR_BITS) - 1))));
-    if (rc == NGSQ_OK && !long_line.empty())
-        rc = sfail(c, NGSQ_ERR_LIMIT, "reading SAM record: record %llu: %s", (unsigned long long)records, long_line.c_str());
+    if (rc == NGSQ_OK && !text.long_line.empty())
+        rc = sfail(c, NGSQ_ERR_LIMIT, "reading SAM record: record %llu: %s", (unsigned long long)records, text.long_line.c_str());
     if (rc == NGSQ_OK) {
         if (const int e = write_bgzf_eof(fd)) rc = write_failed(e);
         enc.comp_bytes += sizeof BGZF_EOF_BLOCK;
@@ -454,7 +244,7 @@ int ngsq_sam_write_bam(ngsq_ctx *c, const char *sam_path, int fd, uint64_t max_r
         out->chunks = chunks;
         out->blocks = enc.blocks;
         out->stored_blocks = enc.stored;
-        out->read_ms = read_ms;
+        out->read_ms = text.read_ms;
         out->h2d_ms = h2d_ms;
         out->parse_ms = parse_ms;
         out->deflate_ms = deflate_ms;

@@ -1,0 +1,62 @@
+// sort_kernels.h -- `ngs convert --sort coordinate` on the device: the keys of resident BAM records, a
+// stable LSD radix sort of (key, index) pairs with 8-bit digits, and the gather of the records into sorted pieces.  Launchers
+// only; sort_kernel.hip has the kernels, sort.cpp the sort's public entry, samsort.cpp the driver.
+#pragma once
+
+#include <hip/hip_runtime_api.h>
+#include <stdint.h>
+
+#include "ingest_consumer.h" // ScanScratch, DevArray
+
+namespace ngsq {
+
+constexpr uint32_t SORT_DIGITS = 8;      // 8-bit digits of a 64-bit key, lowest first
+constexpr uint32_t SORT_BINS = 256;
+constexpr uint32_t SORT_BT = 512;        // threads of a ranking workgroup: eight waves
+constexpr uint32_t SORT_ROUNDS = 8;      // keys a lane ranks: a wave takes 64 consecutive keys per round
+constexpr uint32_t SORT_TILE = SORT_BT * SORT_ROUNDS; // keys one workgroup ranks at a time
+constexpr uint32_t SORT_GATHER_SLACK = 16; // readable bytes behind a record slab: the gather reads whole eight-byte words
+
+inline uint64_t sort_tiles(uint64_t n) { return (n + SORT_TILE - 1) / SORT_TILE; }
+// entries of a pass's (digit, tile) table, digit-major, and one more for the scan's total
+inline uint64_t sort_table_entries(uint64_t n) { return sort_tiles(n) * SORT_BINS + 1; }
+
+// hist[d * 256 + b] = keys whose digit d is b (hist is zeroed here)
+hipError_t launch_sort_histogram(const uint64_t *keys, uint64_t n, unsigned long long *hist, hipStream_t s);
+// table[b * tiles + t] = keys of tile t whose digit `digit` is b, table[256 * tiles] = 0 (then scanned in place by the caller)
+hipError_t launch_sort_count(const uint64_t *keys, uint64_t n, uint32_t digit, uint64_t *table, hipStream_t s);
+// after the scan of table: (keys_in[i], idx_in[i]) goes to the slot its digit and its place among the keys of that digit give
+// it, equal digits in input order.  idx_in == nullptr: the index of a pair is its position (the first pass that runs).
+hipError_t launch_sort_scatter(const uint64_t *keys_in, const uint32_t *idx_in, uint64_t n, uint32_t digit, const uint64_t *table, uint64_t *keys_out,
+                               uint32_t *idx_out, hipStream_t s);
+// idx[i] = i (no pass ran: the input was in order already)
+hipError_t launch_sort_iota(uint32_t *idx, uint64_t n, hipStream_t s);
+
+// The records a chunk's write pass has left at base + off[i], i < n (off[n] = their bytes): record first + i gets its
+// address, its length and its key (unplaced records last).
+hipError_t launch_sort_keys(const uint8_t *base, const uint64_t *off, uint64_t n, uint64_t first, uint64_t *addr, uint32_t *len, uint64_t *key,
+                            hipStream_t s);
+// slen[i] = len[perm[i]], slen[n] = 0 (then scanned in place by the caller into the sorted offsets)
+hipError_t launch_sort_lengths(const uint32_t *len, const uint32_t *perm, uint64_t n, uint64_t *slen, hipStream_t s);
+// after the scan: host[j] (pinned, device address), j <= pieces, = the first record with a byte at or behind j * piece_bytes
+// of the sorted stream (n: none)
+hipError_t launch_sort_bisect(const uint64_t *soff, uint64_t n, uint64_t piece_bytes, uint64_t pieces, unsigned long long *host, hipStream_t s);
+// The bytes [lo, hi) of the sorted stream to out[0, hi - lo): records [a, b) of the sorted order, each clipped to the range.
+// A wave per record; eight-byte stores behind an alignment prologue, the source read as whole words and shifted.
+hipError_t launch_sort_gather(const uint64_t *addr, const uint32_t *perm, const uint64_t *soff, uint64_t a, uint64_t b, uint64_t lo, uint64_t hi,
+                              uint8_t *out, hipStream_t s);
+
+// the device arrays of a sort, beside the caller's keys: the ping-pong's other half, the pass table, the histograms
+struct SortScratch {
+    DevArray<uint64_t> keys_b, table;
+    DevArray<uint32_t> idx[2];
+    DevArray<unsigned long long> hist;
+    ScanScratch scan;
+    uint32_t passes_run = 0, passes_skipped = 0;
+};
+// The sort of keys[0, n) (device; overwritten: they are one half of the ping-pong), n from 1 to 2^32 - 1: *perm, one of
+// sc.idx, holds the input index of the i-th key in ascending order, equal keys in input order.  Waits for the stream once, for the histograms
+// that say which passes run (sort.cpp).
+hipError_t sort_pairs_u64(uint64_t *keys, uint64_t n, SortScratch &sc, hipStream_t s, const uint32_t **perm);
+
+} // namespace ngsq

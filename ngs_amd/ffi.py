@@ -244,6 +244,20 @@ class SamTextReport(C.Structure):
                 ("d2h_ms", C.c_double), ("write_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class SamSortReport(C.Structure):
+    _fields_ = [("records", C.c_uint64), ("header_bytes", C.c_uint64), ("text_bytes", C.c_uint64), ("bam_bytes", C.c_uint64),
+                ("compressed_bytes", C.c_uint64), ("chunks", C.c_uint64), ("pieces", C.c_uint64), ("blocks", C.c_uint64),
+                ("stored_blocks", C.c_uint64), ("resident_bytes", C.c_uint64), ("passes_run", C.c_uint32), ("passes_skipped", C.c_uint32),
+                ("read_ms", C.c_double), ("h2d_ms", C.c_double), ("parse_ms", C.c_double), ("sort_ms", C.c_double),
+                ("gather_ms", C.c_double), ("deflate_ms", C.c_double), ("d2h_ms", C.c_double), ("write_ms", C.c_double),
+                ("total_ms", C.c_double)]
+
+
+# ---- include/ngsq_sort.h ----------------------------------------------------------------------
+class SortReport(C.Structure):
+    _fields_ = [("passes_run", C.c_uint32), ("passes_skipped", C.c_uint32), ("sort_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 # ---- include/ngsq_view.h ----------------------------------------------------------------------
 VIEW_FULL, VIEW_HEADER_ONLY, VIEW_RECORDS_ONLY = 0, 1, 2
 VIEW_MODES = {"full": VIEW_FULL, "header-only": VIEW_HEADER_ONLY, "records-only": VIEW_RECORDS_ONLY}
@@ -458,6 +472,12 @@ PROTOTYPES = {
     "ngsq_sam_check_header": (C.c_int, [C.c_char_p, u32p, C.c_char_p, C.c_size_t]),
     "ngsq_sam_write_bam": (C.c_int, [ctx_p, C.c_char_p, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(SamTextReport)]),
     "ngsq_sam_parse_f32": (C.c_int, [C.c_char_p, C.c_uint32, u32p]),
+    "ngsq_sam_write_sorted_bam": (C.c_int, [ctx_p, C.c_char_p, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(SamSortReport)]),
+    "ngsq_sam_sorted_header": (C.c_int, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    # include/ngsq_sort.h
+    "ngsq_sort_u64_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(SortReport)]),
+    "ngsq_sort_tile_keys": (C.c_uint32, []),
+    "ngsq_sort_last_error": (C.c_char_p, []),
     # include/ngsq_view.h
     "ngsq_bam_query_chunks": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, u32p, u64p, u64p, C.POINTER(ViewChunk), C.c_uint64, u64p]),
     "ngsq_bam_view": (C.c_int, [C.c_void_p, ctx_p, C.c_int, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint64, C.c_uint64,

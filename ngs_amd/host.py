@@ -588,6 +588,63 @@ def sam_to_bam(path: str, out_path: str, device: int = 0, max_records: int = 0, 
         lib.ngsq_destroy(ctx)
 
 
+def sam_to_sorted_bam(path: str, out_path: str, device: int = 0, max_records: int = 0, chunk_bytes: int = 0, piece_bytes: int = 0,
+                      max_resident_bytes: int = 0, lib=None) -> Dict[str, float]:
+    """`ngs convert --gzip device --sort coordinate <SAM> <BAM>` in process (include/ngsq_samtext.h, ngsq_sam_write_sorted_bam): as
+    sam_to_bam, the records in coordinate order, unplaced ones last.  piece_bytes: sorted record bytes gathered and compressed at
+    a time; max_resident_bytes: device memory the records may take (0 each: the library's defaults).  Returns the report."""
+    lib = lib or ffi.load_library()
+    why = C.create_string_buffer(1024)
+    rc = lib.ngsq_sam_check_header(path.encode(), None, why, len(why))   # (before any GPU work, and before out_path exists)
+    if rc != ffi.OK:
+        raise NgsqError(rc, why.value.decode("utf-8", "replace"))
+    cfg = ffi.Config()
+    cfg.struct_size = C.sizeof(ffi.Config)
+    cfg.facets, cfg.device, cfg.n_refs = 0, device, 0
+    ctx = ffi.ctx_p()
+    _check(lib.ngsq_create(C.byref(cfg), C.byref(ctx)), None, lib)
+    try:
+        fd = os.open(out_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o666)
+        try:
+            rep = ffi.SamSortReport()
+            _check(lib.ngsq_sam_write_sorted_bam(ctx, path.encode(), fd, max_records, chunk_bytes, piece_bytes, max_resident_bytes,
+                                                 C.byref(rep)), ctx, lib)
+            return {k: getattr(rep, k) for k, _ in ffi.SamSortReport._fields_}
+        finally:
+            os.close(fd)
+    finally:
+        lib.ngsq_destroy(ctx)
+
+
+def sam_sorted_header(text: bytes, cap: Optional[int] = None, lib=None) -> bytes:
+    """The header text `--sort coordinate` writes for the header text `text` (ngsq_sam_sorted_header, host only).  cap: the
+    output buffer's size (default: what the result takes); NgsqError(BUFFER_TOO_SMALL) when it is too small."""
+    lib = lib or ffi.load_library()
+    text = bytes(text)
+    n = C.c_size_t(0)
+    if cap is None:
+        rc = lib.ngsq_sam_sorted_header(text, len(text), None, 0, C.byref(n))
+        cap = n.value
+    out = C.create_string_buffer(max(cap, 1))
+    rc = lib.ngsq_sam_sorted_header(text, len(text), out, cap, C.byref(n))
+    if rc != ffi.OK:
+        raise NgsqError(rc, f"header text of {n.value} bytes does not fit {cap}")
+    return out.raw[:n.value]
+
+
+def sort_u64(keys, device: int = 0, lib=None):
+    """(perm, report): perm[i] = the index in `keys` (uint64) of the i-th key in ascending order, equal keys in input order --
+    the stable radix sort of `--sort coordinate` alone, on GPU `device` (include/ngsq_sort.h: ngsq_sort_u64_device)."""
+    lib = lib or ffi.load_library()
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    perm = np.empty(len(keys), np.uint32)
+    rep = ffi.SortReport()
+    rc = lib.ngsq_sort_u64_device(device, keys.ctypes.data, len(keys), perm.ctypes.data, C.byref(rep))
+    if rc != ffi.OK:
+        raise NgsqError(rc, (lib.ngsq_sort_last_error() or b"").decode("utf-8", "replace"))
+    return perm, {k: getattr(rep, k) for k, _ in ffi.SortReport._fields_}
+
+
 def sam_parse_f32(text, lib=None) -> int:
     """The bits of the f32 an `f` value of SAM text reads as (ngsq_sam_parse_f32: the kernels' parser, on the host)."""
     lib = lib or ffi.load_library()
