@@ -1363,6 +1363,10 @@ int bam_device_batch_origin(ngsq_bam *b, BatchOrigin *out) {
     out->next_coff = p.next_coff;
     return NGSQ_OK;
 }
+void bam_device_view_sizes(const ngsq_bam *b, uint64_t *chunk_bytes, uint64_t *view_bytes) {
+    *chunk_bytes = b && b->dev ? (uint64_t)b->dev->raw_cap : 0;
+    *view_bytes = *chunk_bytes ? CARRY_MAX + *chunk_bytes : 0;
+}
 } // namespace ngsq
 
 extern "C" {

@@ -222,6 +222,7 @@ int ngsq_bam_open(const char *path, int n_threads, ngsq_bam **out) {
     b->header_text.assign((const char *)b->data.data() + b->data_pos + 8, l_text);
     while (!b->header_text.empty() && b->header_text.back() == '\0') b->header_text.pop_back();
     const uint32_t n_ref = rd32(b->data.data() + b->data_pos + 8 + l_text);
+    b->ref_table.assign((const char *)b->data.data() + b->data_pos + 8 + l_text, 4);
     b->data_pos += 12 + l_text;
     for (uint32_t r = 0; r < n_ref; r++) {
         OPEN_TRY(ensure(b, 4));
@@ -238,6 +239,7 @@ int ngsq_bam_open(const char *path, int n_threads, ngsq_bam **out) {
         const char *nm = (const char *)b->data.data() + b->data_pos + 4;
         b->ref_names.emplace_back(nm, strnlen(nm, l_name));
         b->ref_lens.push_back(rd32(b->data.data() + b->data_pos + 4 + l_name));
+        b->ref_table.append((const char *)b->data.data() + b->data_pos, 8 + (size_t)l_name);
         b->data_pos += 8 + l_name;
     }
 #undef OPEN_TRY

@@ -102,6 +102,7 @@ struct ngsq_bam {
     std::string header_text;
     std::vector<std::string> ref_names;
     std::vector<uint32_t> ref_lens;
+    std::string ref_table;       // the header's bytes from n_ref to the last l_ref, as the file holds them
     uint64_t n_read = 0;
     // batch columns
     std::vector<uint16_t> flag, n_cigar;

@@ -2,12 +2,15 @@
 // text formatted on the GPU by ngsq_bam_write_sam (include/ngsq_sam.h); and, behind the additive `--gzip device`, SAM to BAM
 // (src/convert/sam.rs:26-90): the text parsed and the BGZF written on the GPU by ngsq_sam_write_bam
 // (include/ngsq_samtext.h); with the additive `--sort coordinate` beside it the records are sorted there too
-// (ngsq_sam_write_sorted_bam).  Without the flags every command line answers as a build without that direction.
+// (ngsq_sam_write_sorted_bam); and with both flags BAM to sorted BAM (ngsq_bam_write_sorted_bam,
+// include/ngsq_bamsort.h).  Without the flags every command line answers as a build without that direction.
 #include <fcntl.h>
+#include <sys/stat.h>
 
 #include <algorithm>
 #include <cerrno>
 
+#include "../../../include/ngsq_bamsort.h"
 #include "../../../include/ngsq_sam.h"
 #include "../../../include/ngsq_samtext.h"
 #include "cli.h"
@@ -49,9 +52,11 @@ bool parse_args(int argc, char **argv, int at, ConvertArgs *a) {
                     "          `host` changes nothing [default: host] [possible values: host, device]\n"
                     "      --sort <ORDER>\n"
                     "          Order of the records of a BAM written with --gzip device (additive, this build): `coordinate` sorts them\n"
-                    "          on the GPU, unplaced records last, and writes SO:coordinate [default: none] [possible values: none, coordinate]\n\n"
+                    "          on the GPU, unplaced records last, and writes SO:coordinate; with it BAM to BAM is converted too, a BAM in\n"
+                    "          any record order to a sorted one [default: none] [possible values: none, coordinate]\n\n"
                     "This build converts BAM to SAM, and with --gzip device SAM to BAM: the text is parsed and the BGZF blocks are\n"
-                    "written on the GPU, whose encoder has one setting (-c is checked and takes no part).\n");
+                    "written on the GPU, whose encoder has one setting (-c is checked and takes no part).  With --gzip device and\n"
+                    "--sort coordinate it also converts BAM to BAM: the file is inflated, sorted and compressed on the GPU.\n");
             return false;
         } else if (s == "-n" || s == "--num-records") {
             const std::string v = val("--num-records <USIZE>");
@@ -133,6 +138,47 @@ int sam_to_bam(const ConvertArgs &a, const std::string &from, const std::string 
     return 0;
 }
 
+// BAM to sorted BAM: (1) open the BAM, (2) <TO> must be another file, (3) create it, (4) every record, sorted
+int bam_to_sorted_bam(const ConvertArgs &a, const std::string &from, const std::string &to) {
+    ngsq_bam *bam = nullptr;
+    if (ngsq_bam_open(from.c_str(), 0, &bam) != NGSQ_OK) bail(std::string("opening BAM input file: ") + ngsq_bam_last_error());
+    struct stat sf, stt;
+    if (stat(from.c_str(), &sf) == 0 && stat(to.c_str(), &stt) == 0 && sf.st_dev == stt.st_dev && sf.st_ino == stt.st_ino) {
+        ngsq_bam_close(bam);
+        bail("Conversion from BAM to BAM needs two files: " + to + " is the input");
+    }
+    const int fd = open(to.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
+    if (fd < 0) {
+        const int e = errno;
+        ngsq_bam_close(bam);
+        bail(std::string("opening BAM output file: ") + strerror(e) + " (os error " + std::to_string(e) + ")");
+    }
+    ngsq_ctx *ctx = plain_context(bam, a.device);
+    if (!ctx) {
+        close(fd);
+        bail(ngsq_last_global_error());
+    }
+    const uint64_t max_records = a.has_n ? std::max<unsigned long long>(a.n, 1) : 0;
+    ngsq_bamsort_report rep{};
+    const int rc = ngsq_bam_write_sorted_bam(bam, ctx, fd, max_records, 0, 0, 0, &rep);
+    const std::string msg = rc ? ngsq_bam_last_error() : "";
+    const int close_rc = close(fd), close_errno = errno;
+    ngsq_destroy(ctx);
+    ngsq_bam_close(bam);
+    if (rc) bail(msg);
+    if (close_rc) bail(std::string("writing BAM record: ") + strerror(close_errno) + " (os error " + std::to_string(close_errno) + ")");
+    for (uint64_t m = 1; m <= rep.records / 1000000; m++) logf(2, "  [*] Processed %s records.", with_commas(m * 1000000).c_str());
+    if (g_level >= 3)
+        fprintf(stderr, "[ngs] convert: %llu records in %llu batches and %llu slabs sorted in %u of 8 passes, %llu header bytes -> %llu BAM bytes in "
+                        "%llu pieces, %llu blocks (%llu stored), %llu compressed; ingest %.1f ms, keep %.1f ms, sort %.1f ms, gather %.1f ms, "
+                        "deflate %.1f ms, down %.1f ms, write %.1f ms, total %.1f ms\n",
+                (unsigned long long)rep.records, (unsigned long long)rep.batches, (unsigned long long)rep.slabs, rep.passes_run,
+                (unsigned long long)rep.header_bytes, (unsigned long long)rep.bam_bytes, (unsigned long long)rep.pieces, (unsigned long long)rep.blocks,
+                (unsigned long long)rep.stored_blocks, (unsigned long long)rep.compressed_bytes, rep.scan_ms, rep.keep_ms, rep.sort_ms, rep.gather_ms,
+                rep.deflate_ms, rep.d2h_ms, rep.write_ms, rep.total_ms);
+    return 0;
+}
+
 } // namespace
 
 // argv[at] is "convert".  Exit 0 on success, 1 on every error (anyhow::bail! in the reference).
@@ -155,6 +201,7 @@ int convert_main(int argc, char **argv, int at) {
     const bool reference_only = (ff == "SAM" && tf == "BAM") || (ff == "GFF" && tf == "Block-gzipped GFF") || cram;
     if (cram && !a.has_fasta) bail("--reference-fasta is a required argument when converting to/from a CRAM file");
     if (ff == "SAM" && tf == "BAM" && a.gzip_device) return sam_to_bam(a, from, to);
+    if (ff == "BAM" && tf == "BAM" && a.gzip_device && a.sort_coordinate) return bam_to_sorted_bam(a, from, to);
     if (reference_only)
         bail("Conversion from " + ff + " to " + tf + " is done by the reference `ngs convert` but not by this build, which converts BAM to SAM only");
     if (!(ff == "BAM" && tf == "SAM")) bail("Conversion from " + ff + " to " + tf + " is not currently supported");

@@ -155,5 +155,8 @@ hipError_t launch_rec_var(const uint8_t *raw, const uint64_t *var_base, uint64_t
 
 // bam_device_reader.cpp: the origin of the last batch of ngsq_bam_next_batch_device (valid until the next call)
 int bam_device_batch_origin(ngsq_bam *b, BatchOrigin *out);
+// the sizes of the ingest on this handle (0: it has none): *chunk_bytes = the inflated bytes a chunk holds at most (the size the
+// ingest's buffers follow), *view_bytes = the bytes of a view at most, that chunk and the record carried in front of it
+void bam_device_view_sizes(const ngsq_bam *b, uint64_t *chunk_bytes, uint64_t *view_bytes);
 
 } // namespace ngsq

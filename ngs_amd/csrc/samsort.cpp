@@ -1,34 +1,22 @@
 // samsort.cpp -- include/ngsq_samtext.h: `ngs convert --gzip device --sort coordinate <SAM> <BAM>`.  Three
 // phases on one GPU.  (1) The chunk loop of samtext.cpp through its write pass, but the records stay where they are written, in
-// slabs of device memory, and every record leaves its address, its length and its key behind.  (2) sort_pairs_u64 (sort.cpp)
-// orders (key, record index) pairs.  (3) The sorted stream is cut into pieces of piece_bytes; per piece k_sort_gather copies the
-// records to their sorted offsets, the device DEFLATE encoder makes BGZF blocks of them and the output stage of device_out.h
-// writes them, behind the header's blocks and in front of the EOF block.  Every fault of the text is known before the first
-// byte is written.  The host reads a few words per chunk and per piece and never walks a record.
+// slabs of device memory, and every record leaves its address, its length and its key behind.  (2) and (3) are
+// sort_resident.h's, shared with bamsort.cpp: the sort of (key, record index) pairs, then the sorted stream in pieces through
+// k_sort_gather, the device DEFLATE encoder and the output stage, behind the header's blocks and in front of the EOF block.
+// Every fault of the text is known before the first byte is written.  The host reads a few words per chunk and per piece and
+// never walks a record.
 #include "../../include/ngsq_samtext.h"
 
-#include <memory>
-
 #include "samtext_host.h"
-#include "sort_kernels.h"
+#include "sort_resident.h"
 
 using namespace ngsq;
 
 namespace {
 
-constexpr uint64_t SORT_PIECE_DEFAULT = (uint64_t)64 << 20, SORT_PIECE_MAX = (uint64_t)1 << 30;
-// Device bytes per resident record beside its own: address 8, length 4, key 8, the sort's second key array and its two index
-// arrays 16, the sorted offset 8, and its share of the pass table (half a byte).
-constexpr uint64_t SORT_BYTES_PER_RECORD = 48;
-// What the default budget leaves free of the memory hipMemGetInfo reports: the two text buffers, a chunk's line and offset
-// arrays, the piece buffer, the encoder's scratch and its two block buffers, the unused end of the last slab, and the old
-// halves of the per-record arrays while they double.
-constexpr uint64_t SORT_DEVICE_RESERVE = (uint64_t)4 << 30;
-constexpr uint64_t SORT_SLAB_MIN = (uint64_t)1 << 20, SORT_SLAB_MAX = (uint64_t)512 << 20;
+enum Ev { EV_UP0 = 0, EV_UP1, EV_H0, EV_H1, EV_P0, EV_P1, EV_W0, EV_W1, EV_N };
 
-enum Ev { EV_UP0 = 0, EV_UP1, EV_H0, EV_H1, EV_P0, EV_P1, EV_W0, EV_W1, EV_S0, EV_S1, EV_G0, EV_G1, EV_Z1, EV_N };
-
-enum HostWord : uint32_t { HW_LINES = 0, HW_BYTES, HW_BAD, HW_TEXT, HW_TOTAL, HW_DEFLATE, HW_WORDS = HW_DEFLATE + DEFLATE_HOST_WORDS };
+enum HostWord : uint32_t { HW_LINES = 0, HW_BYTES, HW_BAD, HW_TEXT, HW_WORDS };
 
 } // namespace
 
@@ -67,22 +55,18 @@ int ngsq_sam_write_sorted_bam(ngsq_ctx *c, const char *sam_path, int fd, uint64_
         if (e_ != hipSuccess) return sfail(c, NGSQ_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
     hipStream_t st = c->stream, up = nullptr;
-    DevArray<uint64_t> d_setup, d_tiles, d_start, d_off, d_flist, d_addr, d_key, d_soff;
-    DevArray<uint32_t> d_len;
-    DevArray<uint8_t> d_fmark, d_text[2], d_piece;
-    std::vector<std::unique_ptr<DevArray<uint8_t>>> slabs; // the records: a slab is filled from its front and never moved
-    uint64_t slab_used = 0;
+    DevArray<uint64_t> d_setup, d_tiles, d_start, d_off, d_flist;
+    DevArray<uint8_t> d_fmark, d_text[2];
     ScanScratch scan;
-    SortScratch sort;
-    BgzfEncoder enc; // d_piece's bytes become the blocks of a job
-    JobSlots zslots;
-    MappedBuf hw, hw_first;
+    MappedBuf hw;
     TextChunks text;
     HipEvents<EV_N> ev;
-    DeviceWriter w;
-    StreamDrain drain{st}, drain_up{nullptr, true}; // (behind the arrays: they run first)
-    uint64_t records = 0, text_bytes = 0, rec_bytes = 0, bam_bytes = 0, chunks = 0, pieces = 0, bad = ~0ull, budget = max_resident_bytes;
-    double h2d_ms = 0, parse_ms = 0, sort_ms = 0, gather_ms = 0, deflate_ms = 0;
+    SortResident R; // the slabs, the per-record arrays, phases 2 and 3 (behind the arrays: its drain of st runs first)
+    StreamDrain drain_up{nullptr, true};
+    R.drain.s = st;
+    uint64_t &records = R.records, &rec_bytes = R.rec_bytes;
+    uint64_t text_bytes = 0, chunks = 0, bad = ~0ull, budget = max_resident_bytes;
+    double h2d_ms = 0, parse_ms = 0;
     int limit_rc = NGSQ_OK; // a refusal of phase 1 (its message is set)
 
     auto fill = [&](uint32_t slot, uint64_t *len) -> int {
@@ -101,20 +85,6 @@ int ngsq_sam_write_sorted_bam(ngsq_ctx *c, const char *sam_path, int fd, uint64_
     auto elapsed = [&](int a, int b, double *sum) {
         float ms = 0;
         if (hipEventElapsedTime(&ms, ev.e[a], ev.e[b]) == hipSuccess) *sum += ms;
-    };
-    auto copy_failed = [&](hipError_t e) { return sfail(c, NGSQ_ERR_DEVICE, "copying the BGZF blocks to the host: %s", hipGetErrorString(e)); };
-    // bytes of d_piece through the encoder into its buffer of the job's slot, the blocks to the writer (as samtext.cpp's jobs)
-    auto compress_and_push = [&](uint64_t bytes) -> int {
-        SHIP(enc.launch(zslots.slot(), d_piece.p, bytes, st));
-        SHIP(hipEventRecord(ev.e[EV_Z1], st));
-        SHIP(hipEventSynchronize(ev.e[EV_Z1]));
-        const char *blocks = nullptr;
-        uint64_t n = 0;
-        if (const char *m = enc.collect(zslots.slot(), bytes, &blocks, &n)) return sfail(c, NGSQ_ERR_STATE, "%s", m);
-        elapsed(EV_G1, EV_Z1, &deflate_ms);
-        SHIP(zslots.submit(w, blocks, n, st));
-        bam_bytes += bytes;
-        return NGSQ_OK;
     };
 
     // phase 1: every record written into a slab, nothing compressed
@@ -137,8 +107,7 @@ int ngsq_sam_write_sorted_bam(ngsq_ctx *c, const char *sam_path, int fd, uint64_
         unsigned long long *const hdev = static_cast<unsigned long long *>(hw.dev);
         const unsigned long long *const h = static_cast<const unsigned long long *>(hw.h);
         SHIP(text.start(in.fd, chunk_bytes, H.body_at));
-        enc.h = h + HW_DEFLATE;
-        enc.hdev = hdev + HW_DEFLATE;
+        if (const int rc = R.begin(st)) return sfail(c, rc, "%s", R.err.c_str());
         for (int k = 0; k < EV_N; k++) {
             if (k == EV_UP0 || k == EV_UP1) SHIP(hipEventCreateWithFlags(&ev.e[k], hipEventDisableTiming));
             else SHIP(hipEventCreate(&ev.e[k]));
@@ -193,21 +162,14 @@ int ngsq_sam_write_sorted_bam(ngsq_ctx *c, const char *sam_path, int fd, uint64_
                 break;
             }
             // the records stay: behind the last chunk's in the newest slab, or at the front of a new one
-            if (slabs.empty() || slab_used + bytes + SORT_GATHER_SLACK > slabs.back()->cap) {
-                slabs.emplace_back(new DevArray<uint8_t>());
-                SHIP(slabs.back()->reserve(std::max(slab_bytes, bytes) + SORT_GATHER_SLACK));
-                slab_used = 0;
-            }
-            uint8_t *const dst = slabs.back()->p + slab_used;
-            SHIP(d_addr.reserve_keep(records + n, st));
-            SHIP(d_len.reserve_keep(records + n, st));
-            SHIP(d_key.reserve_keep(records + n, st));
+            uint8_t *dst = nullptr;
+            if (const int rc = R.place(bytes, slab_bytes, ~0u, &dst)) return sfail(c, rc, "%s", R.err.c_str());
+            if (const int rc = R.reserve_records(records + n)) return sfail(c, rc, "%s", R.err.c_str());
             SHIP(hipEventRecord(ev.e[EV_W0], st));
             SHIP(launch_samtext_write(d_text[slot].p, d_start.p, n, refs, d_off.p, dst, fl, st));
-            SHIP(launch_sort_keys(dst, d_off.p, n, records, d_addr.p, d_len.p, d_key.p, st));
+            SHIP(launch_sort_keys(dst, d_off.p, n, records, R.d_addr.p, R.d_len.p, R.d_key.p, st));
             SHIP(hipEventRecord(ev.e[EV_W1], st));
             write_timed = false;
-            slab_used += bytes;
             rec_bytes += bytes;
             records += n;
             text_bytes += h[HW_TEXT];
@@ -227,55 +189,6 @@ int ngsq_sam_write_sorted_bam(ngsq_ctx *c, const char *sam_path, int fd, uint64_
         return NGSQ_OK;
     };
 
-    // phases 2 and 3: the order, then header, pieces
-    auto sort_and_write = [&]() -> int {
-        unsigned long long *const hdev = static_cast<unsigned long long *>(hw.dev);
-        const unsigned long long *const h = static_cast<const unsigned long long *>(hw.h);
-        const uint32_t *perm = nullptr;
-        uint64_t total = 0;
-        const unsigned long long *first = nullptr;
-        if (records) {
-            SHIP(hipEventRecord(ev.e[EV_S0], st));
-            SHIP(sort_pairs_u64(d_key.p, records, sort, st, &perm));
-            // the sorted offsets, and the record every piece begins in
-            SHIP(d_soff.reserve(records + 1));
-            SHIP(launch_sort_lengths(d_len.p, perm, records, d_soff.p, st));
-            SHIP(scan.exclusive_scan(d_soff.p, records + 1, st));
-            SHIP(launch_samtext_word(d_soff.p, records, hdev + HW_TOTAL, st));
-            SHIP(hipEventRecord(ev.e[EV_S1], st));
-            SHIP(hipStreamSynchronize(st));
-            elapsed(EV_S0, EV_S1, &sort_ms);
-            total = h[HW_TOTAL];
-            if (total != rec_bytes) return sfail(c, NGSQ_ERR_STATE, "the sorted records take %llu bytes, the parsed ones %llu", (unsigned long long)total, (unsigned long long)rec_bytes);
-            pieces = (total + piece_bytes - 1) / piece_bytes;
-            if (pieces >= 0x7FFFFFFFull) return sfail(c, NGSQ_ERR_LIMIT, "writing BAM record: more than 2^31 - 2 pieces of %llu bytes", (unsigned long long)piece_bytes);
-            SHIP(hw_first.reserve((pieces + 1) * sizeof(unsigned long long)));
-            SHIP(launch_sort_bisect(d_soff.p, records, piece_bytes, pieces, static_cast<unsigned long long *>(hw_first.dev), st));
-            SHIP(hipStreamSynchronize(st));
-            first = static_cast<const unsigned long long *>(hw_first.h);
-        }
-        SHIP(zslots.create());
-        SHIP(w.start(fd, c->device));
-        // the header's blocks, in front of the first record (as samtools writes them)
-        SHIP(d_piece.reserve(std::max<uint64_t>(hs.size(), std::min(piece_bytes, total)) + DEFLATE_IN_SLACK));
-        SHIP(hipMemcpyAsync(d_piece.p, hs.data(), hs.size(), hipMemcpyHostToDevice, st));
-        SHIP(hipEventRecord(ev.e[EV_G1], st));
-        if (const int rc = compress_and_push(hs.size())) return rc;
-        for (uint64_t j = 0; j < pieces && !w.failed(); j++) {
-            const uint64_t lo = j * piece_bytes, hi = std::min(lo + piece_bytes, total);
-            // records first[j] .. first[j + 1]: the last of them may begin in this piece and end in the next
-            const uint64_t a = first[j], b = std::min<uint64_t>(first[j + 1] + 1, records);
-            if (!zslots.acquire(&w)) return copy_failed(w.herr);
-            SHIP(hipEventRecord(ev.e[EV_G0], st));
-            SHIP(launch_sort_gather(d_addr.p, perm, d_soff.p, a, b, lo, hi, d_piece.p, st));
-            SHIP(hipEventRecord(ev.e[EV_G1], st));
-            if (const int rc = compress_and_push(hi - lo)) return rc;
-            elapsed(EV_G0, EV_G1, &gather_ms);
-        }
-        SHIP(hipStreamSynchronize(st));
-        return NGSQ_OK;
-    };
-
     int rc = parse();
     if (rc == NGSQ_OK && bad != ~0ull)
         rc = sfail(c, NGSQ_ERR_MALFORMED_RECORD, "reading SAM record: record %llu: %s", (unsigned long long)(bad >> ST_ERR_BITS),
@@ -283,37 +196,32 @@ int ngsq_sam_write_sorted_bam(ngsq_ctx *c, const char *sam_path, int fd, uint64_
     if (rc == NGSQ_OK) rc = limit_rc;
     if (rc == NGSQ_OK && !text.long_line.empty())
         rc = sfail(c, NGSQ_ERR_LIMIT, "reading SAM record: record %llu: %s", (unsigned long long)records, text.long_line.c_str());
-    if (rc == NGSQ_OK) rc = sort_and_write();
+    // phases 2 and 3: the order, then header, pieces
+    if (rc == NGSQ_OK) rc = R.sort_and_write(fd, c->device, hs, piece_bytes);
 #undef SHIP
-    auto write_failed = [&](int e) { return sfail(c, NGSQ_ERR_INVALID_ARGUMENT, "writing BAM record: %s (os error %d)", strerror(e), e); };
-    const WriterEnd end = w.end();
-    if (rc == NGSQ_OK && end.herr != hipSuccess) rc = copy_failed(end.herr);
-    if (rc == NGSQ_OK && end.werr) rc = write_failed(end.werr);
-    if (rc == NGSQ_OK) {
-        if (const int e = write_bgzf_eof(fd)) rc = write_failed(e);
-        enc.comp_bytes += sizeof BGZF_EOF_BLOCK;
-    }
+    rc = R.finish(rc, fd);
+    if (rc != NGSQ_OK && !R.err.empty()) sfail(c, rc, "%s", R.err.c_str());
     if (out) {
         out->records = records;
         out->header_bytes = sorted_text.size();
         out->text_bytes = text_bytes;
-        out->bam_bytes = bam_bytes;
-        out->compressed_bytes = enc.comp_bytes;
+        out->bam_bytes = R.bam_bytes;
+        out->compressed_bytes = R.enc.comp_bytes;
         out->chunks = chunks;
-        out->pieces = pieces;
-        out->blocks = enc.blocks;
-        out->stored_blocks = enc.stored;
-        out->resident_bytes = rec_bytes + records * SORT_BYTES_PER_RECORD;
-        out->passes_run = sort.passes_run;
-        out->passes_skipped = SORT_DIGITS - sort.passes_run; // (no records: no pass, as ngsq_sort_u64_device reports it)
+        out->pieces = R.pieces;
+        out->blocks = R.enc.blocks;
+        out->stored_blocks = R.enc.stored;
+        out->resident_bytes = R.resident_bytes();
+        out->passes_run = R.sort.passes_run;
+        out->passes_skipped = SORT_DIGITS - R.sort.passes_run; // (no records: no pass, as ngsq_sort_u64_device reports it)
         out->read_ms = text.read_ms;
         out->h2d_ms = h2d_ms;
         out->parse_ms = parse_ms;
-        out->sort_ms = sort_ms;
-        out->gather_ms = gather_ms;
-        out->deflate_ms = deflate_ms;
-        out->d2h_ms = w.copy_ms;
-        out->write_ms = w.write_ms;
+        out->sort_ms = R.sort_ms;
+        out->gather_ms = R.gather_ms;
+        out->deflate_ms = R.deflate_ms;
+        out->d2h_ms = R.w.copy_ms;
+        out->write_ms = R.w.write_ms;
         out->total_ms = now_ms() - t_begin;
     }
     return rc;

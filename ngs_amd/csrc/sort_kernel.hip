@@ -1,6 +1,9 @@
 // sort_kernel.hip -- the kernels of `ngs convert --sort coordinate`, gfx950, wave64: record keys, a
-// stable LSD radix sort of (key, index) pairs, and the gather of resident records into pieces of the sorted stream.
+// stable LSD radix sort of (key, index) pairs, and the gather of resident records into pieces of the sorted stream; for BAM input
+// (section 20.3) the copy of a batch of the device ingest into a slab.
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
 
 #include "sort_kernels.h"
 
@@ -12,6 +15,7 @@ constexpr uint32_t BT = 256;            // threads of the one-thread-per-item ke
 constexpr uint32_t HIST_PER_THREAD = 16; // keys a thread of k_sort_hist takes at least, when the grid is not capped
 constexpr uint32_t HIST_MAX_BLOCKS = 2048;
 constexpr uint32_t GATHER_WAVES = BT / 64; // records a workgroup of k_sort_gather copies
+constexpr uint32_t KEEP_MAX_BLOCKS = 4096; // of k_sort_keep: its threads stride over the words and over the records
 
 __device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
 __device__ __forceinline__ uint32_t digit_of(uint64_t key, uint32_t digit) { return (uint32_t)(key >> (8u * digit)) & 255u; }
@@ -128,6 +132,42 @@ __global__ __launch_bounds__(BT) void k_sort_keys(const uint8_t *__restrict__ ba
     key[first + i] = (uint64_t)hi << 32 | lo;
 }
 
+// where the records of a batch of the device ingest lie in its view: they are consecutive, so from the first one's first byte
+// to the last one's last
+__global__ __launch_bounds__(64) void k_sort_span(const uint8_t *__restrict__ raw, const uint64_t *__restrict__ rec_off, uint64_t n, unsigned long long *host) {
+    if (blockIdx.x || threadIdx.x) return;
+    const uint64_t last = rec_off[n - 1];
+    host[0] = rec_off[0];
+    host[1] = last + 4u + (uint64_t)load_u32(raw + last);
+}
+
+// The batch's bytes raw[begin, begin + bytes) to dst, which has the source's residue modulo 16 (the launcher checks it): up to 15
+// bytes until both are aligned, 16-byte words, up to 15 bytes behind them; nothing outside either range is read or written.  And
+// what k_sort_keys leaves per record, read from the record's head in the view (it lies at any byte offset).
+__global__ __launch_bounds__(BT) void k_sort_keep(const uint8_t *__restrict__ raw, const uint64_t *__restrict__ rec_off, uint64_t n, uint64_t begin,
+                                                  uint64_t bytes, uint8_t *__restrict__ dst, uint64_t first, uint64_t *__restrict__ addr,
+                                                  uint32_t *__restrict__ len, uint64_t *__restrict__ key) {
+    const uint64_t g = (uint64_t)blockIdx.x * BT + threadIdx.x, stride = (uint64_t)gridDim.x * BT;
+    const uint8_t *src = raw + begin;
+    uint64_t head = (16u - (uint32_t)((uintptr_t)src & 15u)) & 15u;
+    if (head > bytes) head = bytes;
+    const uint64_t words = (bytes - head) >> 4, tail_at = head + words * 16, tail = bytes - tail_at;
+    if (g < head) dst[g] = src[g];
+    if (g < tail) dst[tail_at + g] = src[tail_at + g];
+    const uint4 *sw = reinterpret_cast<const uint4 *>(src + head);
+    uint4 *dw = reinterpret_cast<uint4 *>(dst + head);
+    for (uint64_t k = g; k < words; k += stride) dw[k] = sw[k];
+    for (uint64_t i = g; i < n; i += stride) {
+        const uint64_t o = rec_off[i];
+        const uint8_t *p = raw + o;
+        const int32_t ref_id = (int32_t)load_u32(p + 4), pos = (int32_t)load_u32(p + 8);
+        const uint32_t hi = (ref_id < 0 || pos < 0) ? 0xFFFFFFFFu : (uint32_t)ref_id, lo = (uint32_t)pos + 1u;
+        addr[first + i] = (uint64_t)(uintptr_t)(dst + (o - begin));
+        len[first + i] = 4u + load_u32(p);
+        key[first + i] = (uint64_t)hi << 32 | lo;
+    }
+}
+
 __global__ __launch_bounds__(BT) void k_sort_lengths(const uint32_t *__restrict__ len, const uint32_t *__restrict__ perm, uint64_t n,
                                                      uint64_t *__restrict__ slen) {
     const uint64_t i = (uint64_t)blockIdx.x * BT + threadIdx.x;
@@ -218,6 +258,22 @@ hipError_t launch_sort_keys(const uint8_t *base, const uint64_t *off, uint64_t n
     if (!n) return hipSuccess;
     if (n > 0xFFFFFFFFull) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_sort_keys, dim3(blocks_of(n, BT)), dim3(BT), 0, s, base, off, n, first, addr, len, key);
+    return hipGetLastError();
+}
+
+hipError_t launch_sort_span(const uint8_t *raw, const uint64_t *rec_off, uint64_t n, unsigned long long *host, hipStream_t s) {
+    if (!n) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_sort_span, dim3(1), dim3(64), 0, s, raw, rec_off, n, host);
+    return hipGetLastError();
+}
+
+hipError_t launch_sort_keep(const uint8_t *raw, const uint64_t *rec_off, uint64_t n, uint64_t begin, uint64_t bytes, uint8_t *dst, uint64_t first,
+                            uint64_t *addr, uint32_t *len, uint64_t *key, hipStream_t s) {
+    if (!n) return hipSuccess;
+    if (n > 0xFFFFFFFFull || (((uintptr_t)(raw + begin) ^ (uintptr_t)dst) & 15u)) return hipErrorInvalidValue;
+    const uint64_t want = std::max<uint64_t>((n + BT - 1) / BT, ((bytes >> 4) + BT - 1) / BT);
+    hipLaunchKernelGGL(k_sort_keep, dim3((uint32_t)std::min<uint64_t>(std::max<uint64_t>(want, 1), KEEP_MAX_BLOCKS)), dim3(BT), 0, s, raw, rec_off, n, begin,
+                       bytes, dst, first, addr, len, key);
     return hipGetLastError();
 }
 

@@ -1,6 +1,7 @@
 // sort_kernels.h -- `ngs convert --sort coordinate` on the device: the keys of resident BAM records, a
 // stable LSD radix sort of (key, index) pairs with 8-bit digits, and the gather of the records into sorted pieces.  Launchers
-// only; sort_kernel.hip has the kernels, sort.cpp the sort's public entry, samsort.cpp the driver.
+// only; sort_kernel.hip has the kernels, sort.cpp the sort's public entry, samsort.cpp and bamsort.cpp the drivers (SAM text and
+// BAM in), sort_resident.h the phases they share.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -36,6 +37,15 @@ hipError_t launch_sort_iota(uint32_t *idx, uint64_t n, hipStream_t s);
 // address, its length and its key (unplaced records last).
 hipError_t launch_sort_keys(const uint8_t *base, const uint64_t *off, uint64_t n, uint64_t first, uint64_t *addr, uint32_t *len, uint64_t *key,
                             hipStream_t s);
+// BAM input.  The records of a batch of the device ingest are consecutive in its view `raw`, record i at
+// rec_off[i], i < n, n >= 1: host[0] (pinned, device address) = the view offset of the first one's first byte, host[1] = the
+// offset behind the last one's last byte.
+hipError_t launch_sort_span(const uint8_t *raw, const uint64_t *rec_off, uint64_t n, unsigned long long *host, hipStream_t s);
+// raw[begin, begin + bytes), that range, copied to dst, whose address has the residue modulo 16 of raw + begin (else
+// hipErrorInvalidValue): aligned 16-byte words between up to 15 bytes at either end.  Record first + i gets what launch_sort_keys
+// gives it: its address in dst, its length 4 + block_size and its key.
+hipError_t launch_sort_keep(const uint8_t *raw, const uint64_t *rec_off, uint64_t n, uint64_t begin, uint64_t bytes, uint8_t *dst, uint64_t first,
+                            uint64_t *addr, uint32_t *len, uint64_t *key, hipStream_t s);
 // slen[i] = len[perm[i]], slen[n] = 0 (then scanned in place by the caller into the sorted offsets)
 hipError_t launch_sort_lengths(const uint32_t *len, const uint32_t *perm, uint64_t n, uint64_t *slen, hipStream_t s);
 // after the scan: host[j] (pinned, device address), j <= pieces, = the first record with a byte at or behind j * piece_bytes

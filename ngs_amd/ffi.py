@@ -253,6 +253,15 @@ class SamSortReport(C.Structure):
                 ("total_ms", C.c_double)]
 
 
+# ---- include/ngsq_bamsort.h -------------------------------------------------------------------
+class BamSortReport(C.Structure):
+    _fields_ = [("records", C.c_uint64), ("header_bytes", C.c_uint64), ("bam_bytes", C.c_uint64), ("compressed_bytes", C.c_uint64),
+                ("batches", C.c_uint64), ("slabs", C.c_uint64), ("pieces", C.c_uint64), ("blocks", C.c_uint64),
+                ("stored_blocks", C.c_uint64), ("resident_bytes", C.c_uint64), ("passes_run", C.c_uint32), ("passes_skipped", C.c_uint32),
+                ("scan_ms", C.c_double), ("keep_ms", C.c_double), ("sort_ms", C.c_double), ("gather_ms", C.c_double),
+                ("deflate_ms", C.c_double), ("d2h_ms", C.c_double), ("write_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 # ---- include/ngsq_sort.h ----------------------------------------------------------------------
 class SortReport(C.Structure):
     _fields_ = [("passes_run", C.c_uint32), ("passes_skipped", C.c_uint32), ("sort_ms", C.c_double), ("total_ms", C.c_double)]
@@ -474,6 +483,8 @@ PROTOTYPES = {
     "ngsq_sam_parse_f32": (C.c_int, [C.c_char_p, C.c_uint32, u32p]),
     "ngsq_sam_write_sorted_bam": (C.c_int, [ctx_p, C.c_char_p, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(SamSortReport)]),
     "ngsq_sam_sorted_header": (C.c_int, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    # include/ngsq_bamsort.h
+    "ngsq_bam_write_sorted_bam": (C.c_int, [C.c_void_p, ctx_p, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(BamSortReport)]),
     # include/ngsq_sort.h
     "ngsq_sort_u64_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(SortReport)]),
     "ngsq_sort_tile_keys": (C.c_uint32, []),

@@ -616,6 +616,26 @@ def sam_to_sorted_bam(path: str, out_path: str, device: int = 0, max_records: in
         lib.ngsq_destroy(ctx)
 
 
+def bam_to_sorted_bam(path: str, out_path: str, device: int = 0, max_records: int = 0, batch_records: int = 0, piece_bytes: int = 0,
+                      max_resident_bytes: int = 0, lib=None) -> Dict[str, float]:
+    """`ngs convert --gzip device --sort coordinate <BAM> <BAM>` in process (include/ngsq_bamsort.h): the records of the BAM at
+    `path`, in any order, written to out_path (created or truncated) in coordinate order, unplaced ones last, inflated, sorted
+    and compressed on GPU `device`.  max_records: the first so many records are sorted (0: all; the command line maps `-n N` to
+    max(N, 1)); batch_records: records per ingest batch; piece_bytes: sorted record bytes gathered and compressed at a time;
+    max_resident_bytes: device memory the records may take (0 each: the library's defaults).  Returns the report; NgsqError on
+    an open failure, a file the ingest refuses or records beyond the limits."""
+    lib = lib or ffi.load_library()
+    with _reader_and_plain_context(lib, path, device, "opening BAM input file: ") as (bam, ctx):
+        fd = os.open(out_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o666)
+        try:
+            rep = ffi.BamSortReport()
+            _check_bam(lib.ngsq_bam_write_sorted_bam(bam, ctx, fd, max_records, batch_records, piece_bytes, max_resident_bytes,
+                                                     C.byref(rep)), lib)
+            return {k: getattr(rep, k) for k, _ in ffi.BamSortReport._fields_}
+        finally:
+            os.close(fd)
+
+
 def sam_sorted_header(text: bytes, cap: Optional[int] = None, lib=None) -> bytes:
     """The header text `--sort coordinate` writes for the header text `text` (ngsq_sam_sorted_header, host only).  cap: the
     output buffer's size (default: what the result takes); NgsqError(BUFFER_TOO_SMALL) when it is too small."""
