@@ -11,6 +11,7 @@
 
 #include "ngsq.h"
 #include "ngsq_bam.h"
+#include "ngsq_index.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -44,6 +45,24 @@ typedef struct ngsq_bamsort_report {
  * depends on the input and max_records alone; the compressed bytes also on piece_bytes. */
 int ngsq_bam_write_sorted_bam(ngsq_bam *bam, ngsq_ctx *ctx, int fd, uint64_t max_records, uint64_t batch_records, uint64_t piece_bytes,
                               uint64_t max_resident_bytes, ngsq_bamsort_report *out);
+
+/* ngsq_bam_write_sorted_bam, and the BAI of what it writes at bai_path (`ngs convert --write-index`): byte
+ * for byte the file ngsq_bam_build_index writes for the finished BAM, built from the records while they are resident and from the
+ * encoder's block offsets, without reading the output back.  The bytes written to fd are those of the unindexed call.
+ * index_tile_records: sorted records per launch of the index pass (0: 4 Mi).  index_out (optional): records, n_no_coor, runs and
+ * bins as ngsq_bam_build_index reports them, scan_ms = the device time the index added (index pass, block table, translation),
+ * write_ms = the BAI file.  Refused before any GPU work: an existing bai_path (NGSQ_ERR_INVALID_ARGUMENT, "refusing to overwrite
+ * existing index file: ...").  A record the BAI cannot hold (position beyond 2^29, or reaching more than 1 Mbp beyond the
+ * reference length of the input's binary header): NGSQ_ERR_LIMIT before anything is written to fd, "reading BAM record: record N
+ * (0-based) of the sorted output cannot be held by a BAI: ...".  The index is written beside bai_path and renamed once the EOF
+ * block is out; a failing call leaves nothing there. */
+int ngsq_bam_write_sorted_bam_indexed(ngsq_bam *bam, ngsq_ctx *ctx, int fd, uint64_t max_records, uint64_t batch_records, uint64_t piece_bytes,
+                                      uint64_t max_resident_bytes, ngsq_bamsort_report *out, const char *bai_path, uint64_t index_tile_records,
+                                      ngsq_index_report *index_out);
+
+/* The device time the last indexed call on this thread (this one or ngsq_sam_write_sorted_bam_indexed) spent on its index, in
+ * ms: the index pass, the appends to the block table, the translation to virtual positions.  Null pointers are skipped. */
+void ngsq_sort_index_split(double *pass_ms, double *blocks_ms, double *translate_ms);
 
 #ifdef __cplusplus
 }

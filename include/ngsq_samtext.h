@@ -9,6 +9,7 @@
 #define NGSQ_SAMTEXT_H
 
 #include "ngsq.h"
+#include "ngsq_index.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -65,6 +66,13 @@ typedef struct ngsq_samsort_report {
  * input and max_records alone; the compressed bytes also on piece_bytes. */
 int ngsq_sam_write_sorted_bam(ngsq_ctx *ctx, const char *sam_path, int fd, uint64_t max_records, uint64_t chunk_bytes, uint64_t piece_bytes,
                               uint64_t max_resident_bytes, ngsq_samsort_report *out);
+
+/* ngsq_sam_write_sorted_bam, and the BAI of what it writes at bai_path: the counterpart of ngsq_bam_write_sorted_bam_indexed
+ * (ngsq_bamsort.h), with its arguments, refusals and report; the sequences' lengths are the @SQ LN of the text's header, and
+ * the messages of the index begin "reading SAM record: ". */
+int ngsq_sam_write_sorted_bam_indexed(ngsq_ctx *ctx, const char *sam_path, int fd, uint64_t max_records, uint64_t chunk_bytes, uint64_t piece_bytes,
+                                      uint64_t max_resident_bytes, ngsq_samsort_report *out, const char *bai_path, uint64_t index_tile_records,
+                                      ngsq_index_report *index_out);
 
 /* Host only, no GPU: the header text of a coordinate-sorted file made from text[n].  The first SO: field of the @HD line
  * (the line ngsq_bam_sorted_by_coordinate reads) becomes SO:coordinate, or is appended to that line; its SS: fields whose

@@ -23,7 +23,7 @@ SOURCES = ["kernels.hip", "qual_kernel.hip", "fields_kernel.hip", "cov_scan.hip"
 HEADERS = ["kernels.h", "context.h", "comm.h", "mem_pool.h", "bam_reader.h", "ingest_consumer.h", "ingest_kernels.h", "bgzf.h", "bgzf_crc.h", "deflate_kernels.h", "../../include/ngsq_bgzf.h", "reference_kernels.h", "../../include/ngsq.h",
            "../../include/ngsq_reference.h", "../../include/ngsq_comm.h",
            "../../include/ngsq_shared.h", "../../include/ngsq_synth.h", "../../include/ngsq_bam.h", "../../include/ngsq_stage.h",
-           "bai_kernels.h", "../../include/ngsq_index.h", "sam_kernels.h", "../../include/ngsq_sam.h",
+           "bai_kernels.h", "bai_host.h", "aux_cg.h", "../../include/ngsq_index.h", "sam_kernels.h", "../../include/ngsq_sam.h",
            "derive_kernels.h", "../../include/ngsq_derive.h",
            "device_out.h", "sam_run.h", "view_kernels.h", "view_query.h", "../../include/ngsq_view.h",
            "generate_kernels.h", "generate_draw.h", "reference_load.h", "../../include/ngsq_generate.h",

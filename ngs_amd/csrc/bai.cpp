@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/ngsq_index.h"
+#include "bai_host.h"
 #include "bai_kernels.h"
 #include "bgzf.h"
 #include "context.h"
@@ -77,19 +78,98 @@ void put64(std::vector<uint8_t> &v, uint64_t x) {
 
 constexpr uint64_t BATCH_RECORDS = (uint64_t)1 << 22;
 constexpr uint32_t META_BIN = 37450;      // samtools' metadata pseudo-bin
-constexpr uint32_t LIN_SLACK = 64;        // windows kept beyond @SQ LN: records may reach 1 Mbp past the sequence's end
-constexpr uint32_t LIN_MAX = 1u << 15;    // 2^29 / 16384: the windows of the BAI's coordinate range
 
 } // namespace
+
+std::string ngsq::bai_write_file(const char *bai_path, const BaiTables &T, const std::vector<BaiRun> &R, const std::vector<unsigned long long> &lin,
+                                 uint64_t records, uint64_t final_end, BaiFileCounts *counts) {
+    const uint32_t n_refs = T.n_refs;
+    const uint64_t runs = R.size(), n_win = T.n_win;
+    // ---- the file (SAM/BAM specification 5.2): per sequence its bins in ascending order, each with its runs in file order
+    // (one chunk each: two runs of one bin are never adjacent), the pseudo-bin, the linear index; then n_no_coor
+    std::vector<uint8_t> idx;
+    idx.reserve(16 + runs * 20 + n_win * 8 + n_refs * 64);
+    idx.insert(idx.end(), {'B', 'A', 'I', 1});
+    put32(idx, n_refs);
+    std::vector<uint32_t> cnt(META_BIN, 0), at(META_BIN, 0), touched, order;
+    uint64_t k = 0, n_bins = 0;
+    const unsigned long long *unmapped = T.unmapped(), *n_intv = T.n_intv();
+    for (uint32_t r = 0; r < n_refs; r++) {
+        while (k < runs && R[k].ref >= 0 && (uint32_t)R[k].ref < r) k++; // (sorted: nothing is skipped)
+        const uint64_t a = k;
+        while (k < runs && R[k].ref == (int32_t)r) k++;
+        const uint64_t e = k;
+        if (a == e) {
+            put32(idx, 0);
+        } else {
+            touched.clear();
+            for (uint64_t q = a; q < e; q++)
+                if (cnt[R[q].bin]++ == 0) touched.push_back(R[q].bin);
+            std::sort(touched.begin(), touched.end());
+            uint32_t acc = 0;
+            for (uint32_t bn : touched) {
+                at[bn] = acc;
+                acc += cnt[bn];
+            }
+            order.resize(acc);
+            for (uint64_t q = a; q < e; q++) order[at[R[q].bin]++] = (uint32_t)(q - a);
+            put32(idx, (uint32_t)touched.size() + 1);
+            size_t o = 0;
+            for (uint32_t bn : touched) {
+                put32(idx, bn);
+                put32(idx, cnt[bn]);
+                for (uint32_t j = 0; j < cnt[bn]; j++, o++) {
+                    const uint64_t q = a + order[o];
+                    put64(idx, R[q].start);
+                    put64(idx, q + 1 < runs ? R[q + 1].start : final_end);
+                }
+                cnt[bn] = 0;
+            }
+            n_bins += touched.size();
+            const uint64_t placed = (e < runs ? R[e].rec : records) - R[a].rec;
+            put32(idx, META_BIN);
+            put32(idx, 2);
+            put64(idx, R[a].start);
+            put64(idx, e < runs ? R[e].start : final_end);
+            put64(idx, placed - unmapped[r]);
+            put64(idx, unmapped[r]);
+        }
+        const uint32_t ni = (uint32_t)n_intv[r];
+        put32(idx, ni);
+        for (uint32_t w = 0; w < ni; w++) put64(idx, lin[T.lin_base[r] + w]);
+    }
+    uint64_t n_no_coor = 0;
+    if (runs && R[runs - 1].ref < 0) n_no_coor = records - R[runs - 1].rec;
+    put64(idx, n_no_coor);
+    // written beside its place and renamed: an error leaves nothing at bai_path
+    std::string tmp = std::string(bai_path) + ".XXXXXX";
+    const int fd = mkstemp(&tmp[0]);
+    if (fd < 0) return "creating BAM index output file: cannot create " + tmp;
+    size_t done = 0;
+    while (done < idx.size()) {
+        const ssize_t w = write(fd, idx.data() + done, idx.size() - done);
+        if (w <= 0) break;
+        done += (size_t)w;
+    }
+    const bool written = done == idx.size() && fchmod(fd, 0644) == 0;
+    const bool ok = close(fd) == 0 && written;
+    if (!ok || rename(tmp.c_str(), bai_path) != 0) {
+        unlink(tmp.c_str());
+        return std::string("writing BAM index: cannot write ") + bai_path;
+    }
+    counts->n_no_coor = n_no_coor;
+    counts->bins = n_bins;
+    return "";
+}
 
 extern "C" int ngsq_bam_build_index(ngsq_bam *b, ngsq_ctx *c, const char *bai_path, ngsq_index_report *out) {
     if (!b || !c || !bai_path) return ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "null argument");
     if (out) memset(out, 0, sizeof *out);
     if (const int rc = require_fresh_reader(b, "an index is built")) return rc;
-    struct stat sb;
-    if (stat(bai_path, &sb) == 0)
-        return ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT,
-                             "refusing to overwrite existing index file: %s. Please delete and rerun if you'd like to replace it.", bai_path);
+    {
+        const std::string m = bai_refuse_existing(bai_path);
+        if (!m.empty()) return ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "%s", m.c_str());
+    }
     if (!ngsq_bam_sorted_by_coordinate(b))
         return ngsq_bam_fail(NGSQ_ERR_UNSORTED, "the input BAM must be coordinate-sorted to be indexed");
     const double t0 = now_ms();
@@ -100,52 +180,17 @@ extern "C" int ngsq_bam_build_index(ngsq_bam *b, ngsq_ctx *c, const char *bai_pa
     }
     BHIP(hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    const uint32_t n_refs = (uint32_t)b->ref_lens.size();
-    // ---- device state: linear windows per sequence, unmapped counts, the carry, the run list
-    std::vector<uint64_t> lin_base(n_refs + 1, 0);
-    std::vector<uint32_t> lin_cap(n_refs, 0);
-    for (uint32_t r = 0; r < n_refs; r++) {
-        lin_cap[r] = std::min<uint32_t>((uint32_t)(((uint64_t)b->ref_lens[r] + 16383) >> 14) + LIN_SLACK, LIN_MAX);
-        lin_base[r + 1] = lin_base[r] + lin_cap[r];
-    }
-    const uint64_t n_win = lin_base[n_refs];
-    // one upload of the setup words: [state | lin_base | lin_cap]
-    const size_t state_words = (sizeof(BaiState) + 7) / 8;
-    std::vector<uint64_t> setup(state_words + n_refs + (n_refs + 1) / 2 + 1, 0);
-    {
-        BaiState s0;
-        memset(&s0, 0, sizeof s0);
-        s0.carry[0].endv = hdr_endv;
-        s0.bad_order = ~0ull;
-        s0.bad_limit = ~0ull;
-        memcpy(setup.data(), &s0, sizeof s0);
-        memcpy(setup.data() + state_words, lin_base.data(), n_refs * sizeof(uint64_t));
-        memcpy(setup.data() + state_words + n_refs, lin_cap.data(), n_refs * sizeof(uint32_t));
-    }
-    DevArray<uint64_t> d_setup, d_flag;
-    DevArray<unsigned long long> d_lin, d_unm;
+    // ---- device state: linear windows per sequence, unmapped counts, the carry; then the run list
+    BaiTables T;
+    BHIP(T.create(b->ref_lens.data(), (uint32_t)b->ref_lens.size(), hdr_endv, st));
+    const uint64_t n_win = T.n_win;
+    const BaiLinear &L = T.L;
+    BaiState *const d_state = T.d_state;
+    DevArray<uint64_t> d_flag;
     DevArray<BaiRun> d_tmp, d_runs;
     ScanScratch scan;
-    BHIP(d_setup.reserve(setup.size()));
-    BHIP(d_lin.reserve(n_win + 1));
-    BHIP(d_unm.reserve(n_refs + 1));
-    BHIP(hipMemcpyAsync(d_setup.p, setup.data(), setup.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    BHIP(hipMemsetAsync(d_lin.p, 0xFF, (n_win + 1) * sizeof(unsigned long long), st));
-    BHIP(hipMemsetAsync(d_unm.p, 0, (n_refs + 1) * sizeof(unsigned long long), st));
-    BaiState *d_state = reinterpret_cast<BaiState *>(d_setup.p);
-    BaiLinear L;
-    L.lin = d_lin.p;
-    L.lin_base = d_setup.p + state_words;
-    L.lin_cap = reinterpret_cast<const uint32_t *>(d_setup.p + state_words + n_refs);
-    L.unmapped = d_unm.p;
-    L.n_refs = n_refs;
-    // results the host reads: [count of runs | state words | unmapped | n_intv] in mapped pinned memory
-    MappedBuf pin;
-    const size_t pin_words = 8 + BAI_HOST_STATE_WORDS + 2 * (size_t)n_refs;
-    BHIP(pin.reserve(pin_words * sizeof(unsigned long long)));
-    memset(pin.h, 0, pin_words * sizeof(unsigned long long));
-    const unsigned long long *const pin_h = static_cast<const unsigned long long *>(pin.h);
-    unsigned long long *const host_count = static_cast<unsigned long long *>(pin.dev), *const host_fin = host_count + 8;
+    const unsigned long long *const pin_h = T.pin_h;
+    unsigned long long *const host_count = T.host_count, *const host_fin = T.host_fin;
     hipEvent_t ev = nullptr;
     BHIP(pool_event_get(&ev));
     struct EvPut {
@@ -191,95 +236,26 @@ extern "C" int ngsq_bam_build_index(ngsq_bam *b, ngsq_ctx *c, const char *bai_pa
     R.resize(runs);
     lin.resize(n_win);
     if (runs) BHIP(hipMemcpyAsync(R.data(), d_runs.p, runs * sizeof(BaiRun), hipMemcpyDeviceToHost, st));
-    if (n_win) BHIP(hipMemcpyAsync(lin.data(), d_lin.p, n_win * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    if (n_win) BHIP(hipMemcpyAsync(lin.data(), T.d_lin.p, n_win * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     BHIP(hipStreamSynchronize(st));
-    const unsigned long long *fin = pin_h + 8;
+    const unsigned long long *fin = T.fin();
     if (fin[0] != ~0ull)
         return ngsq_bam_fail(NGSQ_ERR_UNSORTED, "%s: record %llu (0-based) is out of coordinate order: the input BAM must be coordinate-sorted to be indexed",
                              b->path.c_str(), fin[0]);
     if (fin[1] != ~0ull)
-        return ngsq_bam_fail(NGSQ_ERR_LIMIT, "%s: record %llu (0-based) cannot be held by a BAI: its sequence id is out of range, or it reaches "
-                             "beyond position 2^29 or more than 1 Mbp beyond its @SQ LN",
-                             b->path.c_str(), fin[1]);
+        return ngsq_bam_fail(NGSQ_ERR_LIMIT, "%s: record %llu (0-based) %s", b->path.c_str(), fin[1], BAI_LIMIT_TEXT);
     const uint64_t final_end = fin[2];
-    const unsigned long long *unmapped = fin + BAI_HOST_STATE_WORDS, *n_intv = unmapped + n_refs;
     const double t1 = now_ms();
-    // ---- the file (SAM/BAM specification 5.2): per sequence its bins in ascending order, each with its runs in file order
-    // (one chunk each: two runs of one bin are never adjacent), the pseudo-bin, the linear index; then n_no_coor
-    std::vector<uint8_t> idx;
-    idx.reserve(16 + runs * 20 + n_win * 8 + n_refs * 64);
-    idx.insert(idx.end(), {'B', 'A', 'I', 1});
-    put32(idx, n_refs);
-    std::vector<uint32_t> cnt(META_BIN, 0), at(META_BIN, 0), touched, order;
-    uint64_t k = 0, n_bins = 0;
-    for (uint32_t r = 0; r < n_refs; r++) {
-        while (k < runs && R[k].ref >= 0 && (uint32_t)R[k].ref < r) k++; // (sorted: nothing is skipped)
-        const uint64_t a = k;
-        while (k < runs && R[k].ref == (int32_t)r) k++;
-        const uint64_t e = k;
-        if (a == e) {
-            put32(idx, 0);
-        } else {
-            touched.clear();
-            for (uint64_t q = a; q < e; q++)
-                if (cnt[R[q].bin]++ == 0) touched.push_back(R[q].bin);
-            std::sort(touched.begin(), touched.end());
-            uint32_t acc = 0;
-            for (uint32_t bn : touched) {
-                at[bn] = acc;
-                acc += cnt[bn];
-            }
-            order.resize(acc);
-            for (uint64_t q = a; q < e; q++) order[at[R[q].bin]++] = (uint32_t)(q - a);
-            put32(idx, (uint32_t)touched.size() + 1);
-            size_t o = 0;
-            for (uint32_t bn : touched) {
-                put32(idx, bn);
-                put32(idx, cnt[bn]);
-                for (uint32_t j = 0; j < cnt[bn]; j++, o++) {
-                    const uint64_t q = a + order[o];
-                    put64(idx, R[q].start);
-                    put64(idx, q + 1 < runs ? R[q + 1].start : final_end);
-                }
-                cnt[bn] = 0;
-            }
-            n_bins += touched.size();
-            const uint64_t placed = (e < runs ? R[e].rec : records) - R[a].rec;
-            put32(idx, META_BIN);
-            put32(idx, 2);
-            put64(idx, R[a].start);
-            put64(idx, e < runs ? R[e].start : final_end);
-            put64(idx, placed - unmapped[r]);
-            put64(idx, unmapped[r]);
-        }
-        const uint32_t ni = (uint32_t)n_intv[r];
-        put32(idx, ni);
-        for (uint32_t w = 0; w < ni; w++) put64(idx, lin[lin_base[r] + w]);
-    }
-    uint64_t n_no_coor = 0;
-    if (runs && R[runs - 1].ref < 0) n_no_coor = records - R[runs - 1].rec;
-    put64(idx, n_no_coor);
-    // written beside its place and renamed: an error leaves nothing at bai_path
-    std::string tmp = std::string(bai_path) + ".XXXXXX";
-    const int fd = mkstemp(&tmp[0]);
-    if (fd < 0) return ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "creating BAM index output file: cannot create %s", tmp.c_str());
-    size_t done = 0;
-    while (done < idx.size()) {
-        const ssize_t w = write(fd, idx.data() + done, idx.size() - done);
-        if (w <= 0) break;
-        done += (size_t)w;
-    }
-    const bool written = done == idx.size() && fchmod(fd, 0644) == 0;
-    const bool ok = close(fd) == 0 && written;
-    if (!ok || rename(tmp.c_str(), bai_path) != 0) {
-        unlink(tmp.c_str());
-        return ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "writing BAM index: cannot write %s", bai_path);
+    BaiFileCounts counts;
+    {
+        const std::string m = bai_write_file(bai_path, T, R, lin, records, final_end, &counts);
+        if (!m.empty()) return ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "%s", m.c_str());
     }
     if (out) {
         out->records = records;
-        out->n_no_coor = n_no_coor;
+        out->n_no_coor = counts.n_no_coor;
         out->runs = runs;
-        out->bins = n_bins;
+        out->bins = counts.bins;
         out->scan_ms = t1 - t0;
         out->write_ms = now_ms() - t1;
     }

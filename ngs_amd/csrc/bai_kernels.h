@@ -56,4 +56,29 @@ hipError_t launch_bai_gather(const uint64_t *run_off, const BaiRun *tmp_runs, ui
 hipError_t launch_bai_finish(const BaiLinear &lin, const BaiState *state, uint32_t parity, unsigned long long *host, hipStream_t s);
 constexpr uint32_t BAI_HOST_STATE_WORDS = 4;
 
+// ---- the index of a sorted BAM while it is written (sort_resident.h drives these)
+
+// A tile of the sorted order of resident records: record first + i, i < n, is the one at addr[perm[first + i]] (a whole BAM
+// record, block_size first, at any byte alignment) and begins at byte soff[first + i] of the sorted stream (soff[records] = its end).
+struct BaiSorted {
+    const uint64_t *addr;
+    const uint32_t *perm;
+    const uint64_t *soff;
+    uint64_t first, n;
+};
+// launch_bai_records for such a tile.  The positions it leaves (run starts, windows, the carry's endv) are stream offsets plus
+// one, so that k_bai_finish's 0 keeps meaning "no record in front"; BaiRun::rec is the index in the sorted order.
+hipError_t launch_bai_sorted(const BaiSorted &t, BaiState *state, uint32_t parity, const BaiLinear &lin, uint64_t *run_flag, BaiRun *tmp_runs,
+                             hipStream_t s);
+// The file's BGZF blocks that hold records: piece j of piece_bytes stream bytes is blocks [j * blocks_per_piece, ...) of coff,
+// DEFLATE_BLOCK_INPUT stream bytes each, coff their file offsets; the stream has `total` bytes and the EOF block lies at eof_coff.
+struct BaiBlocks {
+    const uint64_t *coff;
+    uint64_t piece_bytes, blocks_per_piece, total, eof_coff;
+};
+// table[i] = base + off[i], i < n_blocks: the encoder's member offsets of a job whose first block lies at file offset base
+hipError_t launch_bai_blocks(const uint64_t *off, uint64_t n_blocks, uint64_t base, uint64_t *table, hipStream_t s);
+// every run's start and every window (after launch_bai_finish) from a stream offset plus one to a virtual position; 0 stays 0
+hipError_t launch_bai_translate(const BaiBlocks &b, BaiRun *runs, uint64_t n_runs, unsigned long long *lin, uint64_t n_win, hipStream_t s);
+
 } // namespace ngsq

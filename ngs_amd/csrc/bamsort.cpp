@@ -23,13 +23,17 @@ int read_failed(int rc) {
     return ngsq_bam_fail(rc, "%s%s", READ_CTX, m.c_str());
 }
 
-} // namespace
-
-extern "C" int ngsq_bam_write_sorted_bam(ngsq_bam *b, ngsq_ctx *c, int fd, uint64_t max_records, uint64_t batch_records, uint64_t piece_bytes,
-                                         uint64_t max_resident_bytes, ngsq_bamsort_report *out) {
+// both entries; bai_path: nullptr, or where the index of the file goes
+int write_sorted(ngsq_bam *b, ngsq_ctx *c, int fd, uint64_t max_records, uint64_t batch_records, uint64_t piece_bytes, uint64_t max_resident_bytes,
+                 ngsq_bamsort_report *out, const char *bai_path, uint64_t index_tile_records, ngsq_index_report *index_out) {
     if (out) memset(out, 0, sizeof *out);
+    if (index_out) memset(index_out, 0, sizeof *index_out);
     if (!b || !c || fd < 0) return ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "null argument");
     if (const int rc = require_fresh_reader(b, "a sorted BAM file is written")) return rc;
+    if (bai_path) { // (before any GPU work, and before a byte goes to fd)
+        const std::string m = bai_refuse_existing(bai_path);
+        if (!m.empty()) return ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "%s", m.c_str());
+    }
     const double t_begin = now_ms();
     if (!batch_records) batch_records = BATCH_RECORDS;
     if (!piece_bytes) piece_bytes = SORT_PIECE_DEFAULT;
@@ -47,6 +51,13 @@ extern "C" int ngsq_bam_write_sorted_bam(ngsq_bam *b, ngsq_ctx *c, int fd, uint6
     HipEvents<2> ev; // around a batch's k_sort_keep
     MappedBuf span;  // where a batch's records lie in the view: two words the host reads
     SortResident R;  // the slabs, the per-record arrays, phases 2 and 3
+    if (bai_path) {
+        R.ix.on = true;
+        R.ix.path = bai_path;
+        R.ix.ctx = READ_CTX;
+        R.ix.tile_records = index_tile_records;
+        R.ix.ref_lens = b->ref_lens; // the binary reference lengths
+    }
     uint64_t batches = 0, budget = max_resident_bytes, slab_bytes = 0, view_bytes = 0;
     double scan_ms = 0, keep_ms = 0;
     bool keep_pending = false; // the last batch's bracket has not been added to keep_ms yet
@@ -144,5 +155,30 @@ extern "C" int ngsq_bam_write_sorted_bam(ngsq_bam *b, ngsq_ctx *c, int fd, uint6
         out->write_ms = R.w.write_ms;
         out->total_ms = now_ms() - t_begin;
     }
+    if (bai_path) R.ix.report(R.records, index_out);
     return rc;
 }
+
+} // namespace
+
+extern "C" {
+
+int ngsq_bam_write_sorted_bam(ngsq_bam *b, ngsq_ctx *c, int fd, uint64_t max_records, uint64_t batch_records, uint64_t piece_bytes,
+                              uint64_t max_resident_bytes, ngsq_bamsort_report *out) {
+    return write_sorted(b, c, fd, max_records, batch_records, piece_bytes, max_resident_bytes, out, nullptr, 0, nullptr);
+}
+
+int ngsq_bam_write_sorted_bam_indexed(ngsq_bam *b, ngsq_ctx *c, int fd, uint64_t max_records, uint64_t batch_records, uint64_t piece_bytes,
+                                      uint64_t max_resident_bytes, ngsq_bamsort_report *out, const char *bai_path, uint64_t index_tile_records,
+                                      ngsq_index_report *index_out) {
+    if (!bai_path) return ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "null argument");
+    return write_sorted(b, c, fd, max_records, batch_records, piece_bytes, max_resident_bytes, out, bai_path, index_tile_records, index_out);
+}
+
+void ngsq_sort_index_split(double *pass_ms, double *blocks_ms, double *translate_ms) {
+    if (pass_ms) *pass_ms = g_sort_index_split.pass_ms;
+    if (blocks_ms) *blocks_ms = g_sort_index_split.blocks_ms;
+    if (translate_ms) *translate_ms = g_sort_index_split.translate_ms;
+}
+
+} // extern "C"

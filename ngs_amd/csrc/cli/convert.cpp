@@ -3,7 +3,8 @@
 // (src/convert/sam.rs:26-90): the text parsed and the BGZF written on the GPU by ngsq_sam_write_bam
 // (include/ngsq_samtext.h); with the additive `--sort coordinate` beside it the records are sorted there too
 // (ngsq_sam_write_sorted_bam); and with both flags BAM to sorted BAM (ngsq_bam_write_sorted_bam,
-// include/ngsq_bamsort.h).  Without the flags every command line answers as a build without that direction.
+// include/ngsq_bamsort.h); with the additive `--write-index` beside those two the BAI of the sorted BAM is
+// written with it.  Without the flags every command line answers as a build without that direction.
 #include <fcntl.h>
 #include <sys/stat.h>
 
@@ -22,6 +23,7 @@ struct ConvertArgs {
     bool has_n = false, has_fasta = false; // (-r and -c take no part in BAM to SAM, as in the reference)
     bool gzip_device = false;              // --gzip device: SAM to BAM is converted, its BGZF written on the GPU
     bool sort_coordinate = false;          // --sort coordinate: ... and its records sorted there
+    bool write_index = false;              // --write-index: ... and <TO>.bai written beside the sorted BAM
     unsigned long long n = 0;
     int device = 0;
 };
@@ -53,7 +55,10 @@ bool parse_args(int argc, char **argv, int at, ConvertArgs *a) {
                     "      --sort <ORDER>\n"
                     "          Order of the records of a BAM written with --gzip device (additive, this build): `coordinate` sorts them\n"
                     "          on the GPU, unplaced records last, and writes SO:coordinate; with it BAM to BAM is converted too, a BAM in\n"
-                    "          any record order to a sorted one [default: none] [possible values: none, coordinate]\n\n"
+                    "          any record order to a sorted one [default: none] [possible values: none, coordinate]\n"
+                    "      --write-index\n"
+                    "          With --gzip device and --sort coordinate (additive, this build): write the index <TO>.bai beside the sorted\n"
+                    "          BAM, the file `ngs index <TO>` would write, built on the GPU while the BAM is written\n\n"
                     "This build converts BAM to SAM, and with --gzip device SAM to BAM: the text is parsed and the BGZF blocks are\n"
                     "written on the GPU, whose encoder has one setting (-c is checked and takes no part).  With --gzip device and\n"
                     "--sort coordinate it also converts BAM to BAM: the file is inflated, sorted and compressed on the GPU.\n");
@@ -85,16 +90,36 @@ bool parse_args(int argc, char **argv, int at, ConvertArgs *a) {
             if (v == "none") a->sort_coordinate = false;
             else if (v == "coordinate") a->sort_coordinate = true;
             else bail("invalid value '" + v + "' for '--sort <ORDER>' [possible values: none, coordinate]");
+        } else if (s == "--write-index") {
+            a->write_index = true;
         } else if (!s.empty() && s[0] == '-' && s != "-") bail("unexpected argument '" + s + "' found");
         else a->pos.push_back(s);
     }
     return true;
 }
 
+// --write-index: an index that exists is refused in the words of `ngs index`, before <TO> is opened
+bool index_exists(const std::string &bai) {
+    struct stat sb;
+    return stat(bai.c_str(), &sb) == 0;
+}
+std::string existing_index_refusal(const std::string &bai) {
+    return "refusing to overwrite existing index file: " + bai + ". Please delete and rerun if you'd like to replace it.";
+}
+
+void log_index_report(const ngsq_index_report &irep) {
+    if (g_level >= 3)
+        fprintf(stderr, "[ngs] convert: index of %llu records (%llu without coordinates), %llu chunks in %llu bins; device %.1f ms, write %.1f ms\n",
+                (unsigned long long)irep.records, (unsigned long long)irep.n_no_coor, (unsigned long long)irep.runs, (unsigned long long)irep.bins,
+                irep.scan_ms, irep.write_ms);
+}
+
 // to_bam_async (sam.rs:26-90): (1) open the SAM and read its header, (2) create the BAM file, (3) the header, (4) every record
 int sam_to_bam(const ConvertArgs &a, const std::string &from, const std::string &to) {
     char why[1024];
     if (ngsq_sam_check_header(from.c_str(), nullptr, why, sizeof why) != NGSQ_OK) bail(why);
+    const std::string bai = to + ".bai";
+    if (a.write_index && index_exists(bai)) bail(existing_index_refusal(bai));
     const int fd = open(to.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
     if (fd < 0) {
         const int e = errno;
@@ -111,8 +136,10 @@ int sam_to_bam(const ConvertArgs &a, const std::string &from, const std::string 
     const uint64_t max_records = a.has_n ? std::max<unsigned long long>(a.n, 1) : 0;
     ngsq_samtext_report rep{};
     ngsq_samsort_report srep{};
-    const int rc = a.sort_coordinate ? ngsq_sam_write_sorted_bam(ctx, from.c_str(), fd, max_records, 0, 0, 0, &srep)
-                                     : ngsq_sam_write_bam(ctx, from.c_str(), fd, max_records, 0, &rep);
+    ngsq_index_report irep{};
+    const int rc = a.write_index       ? ngsq_sam_write_sorted_bam_indexed(ctx, from.c_str(), fd, max_records, 0, 0, 0, &srep, bai.c_str(), 0, &irep)
+                   : a.sort_coordinate ? ngsq_sam_write_sorted_bam(ctx, from.c_str(), fd, max_records, 0, 0, 0, &srep)
+                                       : ngsq_sam_write_bam(ctx, from.c_str(), fd, max_records, 0, &rep);
     const std::string msg = rc ? ngsq_last_error(ctx) : "";
     const int close_rc = close(fd), close_errno = errno;
     ngsq_destroy(ctx);
@@ -135,6 +162,7 @@ int sam_to_bam(const ConvertArgs &a, const std::string &from, const std::string 
                 (unsigned long long)rep.text_bytes, (unsigned long long)rep.bam_bytes, (unsigned long long)rep.blocks,
                 (unsigned long long)rep.stored_blocks, (unsigned long long)rep.compressed_bytes, rep.read_ms, rep.h2d_ms, rep.parse_ms,
                 rep.deflate_ms, rep.d2h_ms, rep.write_ms, rep.total_ms);
+    if (a.write_index) log_index_report(irep);
     return 0;
 }
 
@@ -146,6 +174,11 @@ int bam_to_sorted_bam(const ConvertArgs &a, const std::string &from, const std::
     if (stat(from.c_str(), &sf) == 0 && stat(to.c_str(), &stt) == 0 && sf.st_dev == stt.st_dev && sf.st_ino == stt.st_ino) {
         ngsq_bam_close(bam);
         bail("Conversion from BAM to BAM needs two files: " + to + " is the input");
+    }
+    const std::string bai = to + ".bai";
+    if (a.write_index && index_exists(bai)) {
+        ngsq_bam_close(bam);
+        bail(existing_index_refusal(bai));
     }
     const int fd = open(to.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
     if (fd < 0) {
@@ -160,7 +193,9 @@ int bam_to_sorted_bam(const ConvertArgs &a, const std::string &from, const std::
     }
     const uint64_t max_records = a.has_n ? std::max<unsigned long long>(a.n, 1) : 0;
     ngsq_bamsort_report rep{};
-    const int rc = ngsq_bam_write_sorted_bam(bam, ctx, fd, max_records, 0, 0, 0, &rep);
+    ngsq_index_report irep{};
+    const int rc = a.write_index ? ngsq_bam_write_sorted_bam_indexed(bam, ctx, fd, max_records, 0, 0, 0, &rep, bai.c_str(), 0, &irep)
+                                 : ngsq_bam_write_sorted_bam(bam, ctx, fd, max_records, 0, 0, 0, &rep);
     const std::string msg = rc ? ngsq_bam_last_error() : "";
     const int close_rc = close(fd), close_errno = errno;
     ngsq_destroy(ctx);
@@ -176,6 +211,7 @@ int bam_to_sorted_bam(const ConvertArgs &a, const std::string &from, const std::
                 (unsigned long long)rep.header_bytes, (unsigned long long)rep.bam_bytes, (unsigned long long)rep.pieces, (unsigned long long)rep.blocks,
                 (unsigned long long)rep.stored_blocks, (unsigned long long)rep.compressed_bytes, rep.scan_ms, rep.keep_ms, rep.sort_ms, rep.gather_ms,
                 rep.deflate_ms, rep.d2h_ms, rep.write_ms, rep.total_ms);
+    if (a.write_index) log_index_report(irep);
     return 0;
 }
 
@@ -200,6 +236,9 @@ int convert_main(int argc, char **argv, int at) {
                       (ff == "CRAM" && tf == "BAM");
     const bool reference_only = (ff == "SAM" && tf == "BAM") || (ff == "GFF" && tf == "Block-gzipped GFF") || cram;
     if (cram && !a.has_fasta) bail("--reference-fasta is a required argument when converting to/from a CRAM file");
+    // (additive) the index is written where a sorted path is reached; refused before any file is opened
+    if (a.write_index && !(a.gzip_device && a.sort_coordinate && tf == "BAM" && (ff == "SAM" || ff == "BAM")))
+        bail("--write-index needs --gzip device and --sort coordinate and a BAM to write");
     if (ff == "SAM" && tf == "BAM" && a.gzip_device) return sam_to_bam(a, from, to);
     if (ff == "BAM" && tf == "BAM" && a.gzip_device && a.sort_coordinate) return bam_to_sorted_bam(a, from, to);
     if (reference_only)

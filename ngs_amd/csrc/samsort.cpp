@@ -18,14 +18,17 @@ enum Ev { EV_UP0 = 0, EV_UP1, EV_H0, EV_H1, EV_P0, EV_P1, EV_W0, EV_W1, EV_N };
 
 enum HostWord : uint32_t { HW_LINES = 0, HW_BYTES, HW_BAD, HW_TEXT, HW_WORDS };
 
-} // namespace
-
-extern "C" {
-
-int ngsq_sam_write_sorted_bam(ngsq_ctx *c, const char *sam_path, int fd, uint64_t max_records, uint64_t chunk_bytes, uint64_t piece_bytes,
-                              uint64_t max_resident_bytes, ngsq_samsort_report *out) {
+// both entries; bai_path: nullptr, or where the index of the file goes
+int write_sorted(ngsq_ctx *c, const char *sam_path, int fd, uint64_t max_records, uint64_t chunk_bytes, uint64_t piece_bytes,
+                 uint64_t max_resident_bytes, ngsq_samsort_report *out, const char *bai_path, uint64_t index_tile_records,
+                 ngsq_index_report *index_out) {
     if (out) memset(out, 0, sizeof *out);
+    if (index_out) memset(index_out, 0, sizeof *index_out);
     if (!c || !sam_path || fd < 0) return sfail(c, NGSQ_ERR_INVALID_ARGUMENT, "null argument");
+    if (bai_path) { // (before any GPU work, and before a byte goes to fd)
+        const std::string m = bai_refuse_existing(bai_path);
+        if (!m.empty()) return sfail(c, NGSQ_ERR_INVALID_ARGUMENT, "%s", m.c_str());
+    }
     const double t_begin = now_ms();
     if (!chunk_bytes) chunk_bytes = ST_CHUNK_DEFAULT;
     chunk_bytes = std::min(chunk_bytes, ST_CHUNK_MAX);
@@ -64,6 +67,13 @@ int ngsq_sam_write_sorted_bam(ngsq_ctx *c, const char *sam_path, int fd, uint64_
     SortResident R; // the slabs, the per-record arrays, phases 2 and 3 (behind the arrays: its drain of st runs first)
     StreamDrain drain_up{nullptr, true};
     R.drain.s = st;
+    if (bai_path) {
+        R.ix.on = true;
+        R.ix.path = bai_path;
+        R.ix.ctx = "reading SAM record: ";
+        R.ix.tile_records = index_tile_records;
+        R.ix.ref_lens = H.lens; // @SQ LN
+    }
     uint64_t &records = R.records, &rec_bytes = R.rec_bytes;
     uint64_t text_bytes = 0, chunks = 0, bad = ~0ull, budget = max_resident_bytes;
     double h2d_ms = 0, parse_ms = 0;
@@ -224,7 +234,24 @@ int ngsq_sam_write_sorted_bam(ngsq_ctx *c, const char *sam_path, int fd, uint64_
         out->write_ms = R.w.write_ms;
         out->total_ms = now_ms() - t_begin;
     }
+    if (bai_path) R.ix.report(records, index_out);
     return rc;
+}
+
+} // namespace
+
+extern "C" {
+
+int ngsq_sam_write_sorted_bam(ngsq_ctx *c, const char *sam_path, int fd, uint64_t max_records, uint64_t chunk_bytes, uint64_t piece_bytes,
+                              uint64_t max_resident_bytes, ngsq_samsort_report *out) {
+    return write_sorted(c, sam_path, fd, max_records, chunk_bytes, piece_bytes, max_resident_bytes, out, nullptr, 0, nullptr);
+}
+
+int ngsq_sam_write_sorted_bam_indexed(ngsq_ctx *c, const char *sam_path, int fd, uint64_t max_records, uint64_t chunk_bytes, uint64_t piece_bytes,
+                                      uint64_t max_resident_bytes, ngsq_samsort_report *out, const char *bai_path, uint64_t index_tile_records,
+                                      ngsq_index_report *index_out) {
+    if (!bai_path) return sfail(c, NGSQ_ERR_INVALID_ARGUMENT, "null argument");
+    return write_sorted(c, sam_path, fd, max_records, chunk_bytes, piece_bytes, max_resident_bytes, out, bai_path, index_tile_records, index_out);
 }
 
 } // extern "C"

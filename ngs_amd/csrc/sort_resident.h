@@ -4,6 +4,9 @@
 // sorted stream is cut into pieces of piece_bytes, per piece k_sort_gather copies the records to their sorted offsets, the
 // device DEFLATE encoder makes BGZF blocks of them and the output stage of device_out.h writes them, behind the header's blocks
 // and in front of the EOF block.  A failure leaves its code and its message in `err`; the driver reports it through its own channel.
+// With `ix.on` (--write-index) the BAI of the file is built on the way: an index pass over the sorted order
+// before the writer starts, the encoder's block offsets kept per piece, and one translation from stream offsets to virtual
+// positions behind the last piece; bai.cpp's writer makes the file once the EOF block is out.
 #pragma once
 
 #include <cstdarg>
@@ -11,6 +14,8 @@
 #include <string>
 #include <vector>
 
+#include "../../include/ngsq_index.h"
+#include "bai_host.h"
 #include "device_out.h"
 #include "samtext_kernels.h" // launch_samtext_word
 #include "sort_kernels.h"
@@ -26,9 +31,49 @@ constexpr uint64_t SORT_BYTES_PER_RECORD = 48;
 // halves of the per-record arrays while they double.
 constexpr uint64_t SORT_DEVICE_RESERVE = (uint64_t)4 << 30;
 constexpr uint64_t SORT_SLAB_MIN = (uint64_t)1 << 20, SORT_SLAB_MAX = (uint64_t)512 << 20;
+// Sorted records per tile of the index pass: the ingest's batch size, so that the tile buffers (a run flag and a tentative run
+// per record, 32 bytes) are section 12.2's, 128 MiB, inside SORT_DEVICE_RESERVE.
+constexpr uint64_t SORT_INDEX_TILE = (uint64_t)1 << 22;
+
+// the device times of the last indexed call on this thread, in ms (ngsq_sort_index_split)
+struct SortIndexSplit {
+    double pass_ms = 0, blocks_ms = 0, translate_ms = 0;
+};
+inline thread_local SortIndexSplit g_sort_index_split;
+
+// What --write-index adds to a SortResident.  The driver sets `on`, the path, the tile, the sequences' lengths and its message
+// prefix before sort_and_write; everything else is the shared phases'.
+struct SortIndex {
+    bool on = false;
+    std::string path, ctx;       // <TO>.bai; "reading BAM record: " or "reading SAM record: "
+    uint64_t tile_records = SORT_INDEX_TILE;
+    std::vector<uint32_t> ref_lens;
+    BaiTables T;
+    DevArray<uint64_t> d_flag, d_table; // a tile's run flags; the file's block table
+    DevArray<BaiRun> d_tmp, d_runs;     // a tile's tentative runs; the run list
+    ScanScratch scan;
+    uint64_t runs = 0, blocks_per_piece = 0, final_end = 0;
+    bool append_pending = false;
+    std::vector<BaiRun> R; // what the end copies to the host: the run list and the windows, translated
+    std::vector<unsigned long long> lin;
+    SortIndexSplit ms;
+    double write_ms = 0;
+    BaiFileCounts counts;
+
+    void report(uint64_t records, ngsq_index_report *out) const {
+        g_sort_index_split = ms;
+        if (!out) return;
+        out->records = records;
+        out->n_no_coor = counts.n_no_coor;
+        out->runs = runs;
+        out->bins = counts.bins;
+        out->scan_ms = ms.pass_ms + ms.blocks_ms + ms.translate_ms;
+        out->write_ms = write_ms;
+    }
+};
 
 struct SortResident {
-    enum Ev { EV_S0 = 0, EV_S1, EV_G0, EV_G1, EV_Z1, EV_N };
+    enum Ev { EV_S0 = 0, EV_S1, EV_G0, EV_G1, EV_Z1, EV_I0, EV_I1, EV_B0, EV_B1, EV_N };
     enum HostWord : uint32_t { HW_TOTAL = 0, HW_DEFLATE, HW_WORDS = HW_DEFLATE + DEFLATE_HOST_WORDS };
 
     hipStream_t st = nullptr;
@@ -50,6 +95,7 @@ struct SortResident {
     DeviceWriter w;
     uint64_t bam_bytes = 0, pieces = 0;
     double sort_ms = 0, gather_ms = 0, deflate_ms = 0;
+    SortIndex ix;
     int code = 0;
     std::string err;
     StreamDrain drain; // (behind the arrays: it runs first)
@@ -109,17 +155,85 @@ struct SortResident {
         return NGSQ_OK;
     }
 
-    // bytes of d_piece through the encoder into its buffer of the job's slot, the blocks to the writer (as samtext.cpp's jobs)
-    int compress_and_push(uint64_t bytes) {
+    // the time of the last append to the block table, once the stream has passed it
+    void add_append_time() {
+        if (ix.append_pending) elapsed(EV_B0, EV_B1, &ix.ms.blocks_ms);
+        ix.append_pending = false;
+    }
+
+    // The index pass: tiles of the sorted order through k_bai_sorted, the scan and the gather, the carry
+    // from tile to tile, then k_bai_finish.  Positions are offsets in the sorted stream plus one.  A record the BAI cannot hold
+    // is refused here, before the writer starts.
+    int index_pass(const uint32_t *perm) {
+        BaiTables &T = ix.T;
+        SRHIP(hipEventRecord(ev.e[EV_I0], st));
+        SRHIP(T.create(ix.ref_lens.data(), (uint32_t)ix.ref_lens.size(), 1, st));
+        const uint64_t tile = ix.tile_records ? ix.tile_records : SORT_INDEX_TILE;
+        uint32_t parity = 0;
+        for (uint64_t k0 = 0; k0 < records; k0 += tile) {
+            const uint64_t n = std::min(tile, records - k0);
+            SRHIP(ix.d_flag.reserve(n + 1));
+            SRHIP(ix.d_tmp.reserve(n));
+            SRHIP(ix.d_runs.reserve_keep(ix.runs + n, st));
+            const BaiSorted t{d_addr.p, perm, d_soff.p, k0, n};
+            SRHIP(launch_bai_sorted(t, T.d_state, parity, T.L, ix.d_flag.p, ix.d_tmp.p, st));
+            SRHIP(ix.scan.exclusive_scan(ix.d_flag.p, n + 1, st));
+            SRHIP(launch_bai_gather(ix.d_flag.p, ix.d_tmp.p, n, ix.d_runs.p, ix.runs, T.host_count, st));
+            SRHIP(hipStreamSynchronize(st)); // (the run list grows by what the tile gave it)
+            ix.runs = T.pin_h[0];
+            parity ^= 1u;
+        }
+        SRHIP(launch_bai_finish(T.L, T.d_state, parity, T.host_fin, st));
+        SRHIP(hipEventRecord(ev.e[EV_I1], st));
+        SRHIP(hipStreamSynchronize(st));
+        elapsed(EV_I0, EV_I1, &ix.ms.pass_ms);
+        const unsigned long long *fin = T.fin();
+        // (the order check of `ngs index`, kept as a check of the sort itself)
+        if (fin[0] != ~0ull)
+            return fail(NGSQ_ERR_STATE, "%srecord %llu (0-based) of the sorted output is out of coordinate order", ix.ctx.c_str(), fin[0]);
+        if (fin[1] != ~0ull)
+            return fail(NGSQ_ERR_LIMIT, "%srecord %llu (0-based) of the sorted output %s", ix.ctx.c_str(), fin[1], BAI_LIMIT_TEXT);
+        return NGSQ_OK;
+    }
+
+    // Behind the last piece: the run starts and the filled windows become virtual positions through the block table, and come
+    // to the host.  (Every piece has been collected: enc.comp_bytes is where the EOF block will lie.)
+    int index_translate(uint64_t piece_bytes, uint64_t total) {
+        BaiTables &T = ix.T;
+        add_append_time();
+        const BaiBlocks B{ix.d_table.p, piece_bytes, ix.blocks_per_piece, total, enc.comp_bytes};
+        SRHIP(hipEventRecord(ev.e[EV_I0], st));
+        SRHIP(launch_bai_translate(B, ix.d_runs.p, ix.runs, T.d_lin.p, T.n_win, st));
+        SRHIP(hipEventRecord(ev.e[EV_I1], st));
+        ix.R.resize(ix.runs);
+        ix.lin.resize(T.n_win);
+        if (ix.runs) SRHIP(hipMemcpyAsync(ix.R.data(), ix.d_runs.p, ix.runs * sizeof(BaiRun), hipMemcpyDeviceToHost, st));
+        if (T.n_win) SRHIP(hipMemcpyAsync(ix.lin.data(), T.d_lin.p, T.n_win * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        SRHIP(hipStreamSynchronize(st));
+        elapsed(EV_I0, EV_I1, &ix.ms.translate_ms);
+        ix.final_end = enc.comp_bytes << 16;
+        return NGSQ_OK;
+    }
+
+    // bytes of d_piece through the encoder into its buffer of the job's slot, the blocks to the writer (as samtext.cpp's jobs);
+    // table (optional): the job's block offsets in the file go there, behind the hand-over
+    int compress_and_push(uint64_t bytes, uint64_t *table = nullptr) {
         SRHIP(enc.launch(zslots.slot(), d_piece.p, bytes, st));
         SRHIP(hipEventRecord(ev.e[EV_Z1], st));
         SRHIP(hipEventSynchronize(ev.e[EV_Z1]));
+        add_append_time(); // (the last job's append lies in front of this encoder)
         const char *blocks = nullptr;
         uint64_t n = 0;
         if (const char *m = enc.collect(zslots.slot(), bytes, &blocks, &n)) return fail(NGSQ_ERR_STATE, "%s", m);
         elapsed(EV_G1, EV_Z1, &deflate_ms);
         SRHIP(zslots.submit(w, blocks, n, st));
         bam_bytes += bytes;
+        if (table) {
+            SRHIP(hipEventRecord(ev.e[EV_B0], st));
+            SRHIP(launch_bai_blocks(enc.sc.off.p, deflate_blocks(bytes), enc.comp_bytes - n, table, st));
+            SRHIP(hipEventRecord(ev.e[EV_B1], st));
+            ix.append_pending = true;
+        }
         return NGSQ_OK;
     }
 
@@ -151,6 +265,11 @@ struct SortResident {
             SRHIP(hipStreamSynchronize(st));
             first = static_cast<const unsigned long long *>(hw_first.h);
         }
+        if (ix.on) {
+            if (const int rc = index_pass(perm)) return rc;
+            ix.blocks_per_piece = deflate_blocks(piece_bytes);
+            SRHIP(ix.d_table.reserve(pieces * ix.blocks_per_piece + 1));
+        }
         SRHIP(zslots.create());
         SRHIP(w.start(fd, device));
         // the header's blocks, in front of the first record (as samtools writes them)
@@ -166,10 +285,12 @@ struct SortResident {
             SRHIP(hipEventRecord(ev.e[EV_G0], st));
             SRHIP(launch_sort_gather(d_addr.p, perm, d_soff.p, a, b, lo, hi, d_piece.p, st));
             SRHIP(hipEventRecord(ev.e[EV_G1], st));
-            if (const int rc = compress_and_push(hi - lo)) return rc;
+            if (const int rc = compress_and_push(hi - lo, ix.on ? ix.d_table.p + j * ix.blocks_per_piece : nullptr)) return rc;
             elapsed(EV_G0, EV_G1, &gather_ms);
         }
         SRHIP(hipStreamSynchronize(st));
+        if (ix.on && !w.failed())
+            if (const int rc = index_translate(piece_bytes, total)) return rc;
         return NGSQ_OK;
     }
 #undef SRHIP
@@ -183,6 +304,13 @@ struct SortResident {
         if (rc == NGSQ_OK) {
             if (const int e = write_bgzf_eof(fd)) rc = write_failed(e);
             enc.comp_bytes += sizeof BGZF_EOF_BLOCK;
+        }
+        // the index, once the file it describes is complete: beside its place and renamed (bai.cpp's writer)
+        if (rc == NGSQ_OK && ix.on) {
+            const double t0 = now_ms();
+            const std::string m = bai_write_file(ix.path.c_str(), ix.T, ix.R, ix.lin, records, ix.final_end, &ix.counts);
+            ix.write_ms = now_ms() - t0;
+            if (!m.empty()) rc = fail(NGSQ_ERR_INVALID_ARGUMENT, "%s", m.c_str());
         }
         return rc;
     }

@@ -482,9 +482,14 @@ PROTOTYPES = {
     "ngsq_sam_write_bam": (C.c_int, [ctx_p, C.c_char_p, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(SamTextReport)]),
     "ngsq_sam_parse_f32": (C.c_int, [C.c_char_p, C.c_uint32, u32p]),
     "ngsq_sam_write_sorted_bam": (C.c_int, [ctx_p, C.c_char_p, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(SamSortReport)]),
+    "ngsq_sam_write_sorted_bam_indexed": (C.c_int, [ctx_p, C.c_char_p, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(SamSortReport),
+                                                    C.c_char_p, C.c_uint64, C.POINTER(IndexReport)]),
     "ngsq_sam_sorted_header": (C.c_int, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     # include/ngsq_bamsort.h
     "ngsq_bam_write_sorted_bam": (C.c_int, [C.c_void_p, ctx_p, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(BamSortReport)]),
+    "ngsq_bam_write_sorted_bam_indexed": (C.c_int, [C.c_void_p, ctx_p, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(BamSortReport),
+                                                    C.c_char_p, C.c_uint64, C.POINTER(IndexReport)]),
+    "ngsq_sort_index_split": (None, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     # include/ngsq_sort.h
     "ngsq_sort_u64_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(SortReport)]),
     "ngsq_sort_tile_keys": (C.c_uint32, []),

@@ -588,11 +588,22 @@ def sam_to_bam(path: str, out_path: str, device: int = 0, max_records: int = 0, 
         lib.ngsq_destroy(ctx)
 
 
+def _index_report(rep, lib) -> Dict[str, float]:
+    """The index report of an indexed sort, with the device times of its three steps (ngsq_sort_index_split)."""
+    out = {k: getattr(rep, k) for k, _ in ffi.IndexReport._fields_}
+    ms = [C.c_double(0), C.c_double(0), C.c_double(0)]
+    lib.ngsq_sort_index_split(*[C.byref(m) for m in ms])
+    out["pass_ms"], out["blocks_ms"], out["translate_ms"] = (m.value for m in ms)
+    return out
+
+
 def sam_to_sorted_bam(path: str, out_path: str, device: int = 0, max_records: int = 0, chunk_bytes: int = 0, piece_bytes: int = 0,
-                      max_resident_bytes: int = 0, lib=None) -> Dict[str, float]:
+                      max_resident_bytes: int = 0, lib=None, bai_path: Optional[str] = None, index_tile_records: int = 0):
     """`ngs convert --gzip device --sort coordinate <SAM> <BAM>` in process (include/ngsq_samtext.h, ngsq_sam_write_sorted_bam): as
     sam_to_bam, the records in coordinate order, unplaced ones last.  piece_bytes: sorted record bytes gathered and compressed at
-    a time; max_resident_bytes: device memory the records may take (0 each: the library's defaults).  Returns the report."""
+    a time; max_resident_bytes: device memory the records may take (0 each: the library's defaults).  Returns the report.
+    bai_path: `--write-index` (ngsq_sam_write_sorted_bam_indexed): the BAI of out_path is written there, index_tile_records sorted
+    records per launch of the index pass (0: the library's default); returns (sort report, index report)."""
     lib = lib or ffi.load_library()
     why = C.create_string_buffer(1024)
     rc = lib.ngsq_sam_check_header(path.encode(), None, why, len(why))   # (before any GPU work, and before out_path exists)
@@ -607,9 +618,14 @@ def sam_to_sorted_bam(path: str, out_path: str, device: int = 0, max_records: in
         fd = os.open(out_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o666)
         try:
             rep = ffi.SamSortReport()
-            _check(lib.ngsq_sam_write_sorted_bam(ctx, path.encode(), fd, max_records, chunk_bytes, piece_bytes, max_resident_bytes,
-                                                 C.byref(rep)), ctx, lib)
-            return {k: getattr(rep, k) for k, _ in ffi.SamSortReport._fields_}
+            if bai_path is None:
+                _check(lib.ngsq_sam_write_sorted_bam(ctx, path.encode(), fd, max_records, chunk_bytes, piece_bytes, max_resident_bytes,
+                                                     C.byref(rep)), ctx, lib)
+                return {k: getattr(rep, k) for k, _ in ffi.SamSortReport._fields_}
+            irep = ffi.IndexReport()
+            _check(lib.ngsq_sam_write_sorted_bam_indexed(ctx, path.encode(), fd, max_records, chunk_bytes, piece_bytes, max_resident_bytes,
+                                                         C.byref(rep), bai_path.encode(), index_tile_records, C.byref(irep)), ctx, lib)
+            return {k: getattr(rep, k) for k, _ in ffi.SamSortReport._fields_}, _index_report(irep, lib)
         finally:
             os.close(fd)
     finally:
@@ -617,21 +633,28 @@ def sam_to_sorted_bam(path: str, out_path: str, device: int = 0, max_records: in
 
 
 def bam_to_sorted_bam(path: str, out_path: str, device: int = 0, max_records: int = 0, batch_records: int = 0, piece_bytes: int = 0,
-                      max_resident_bytes: int = 0, lib=None) -> Dict[str, float]:
+                      max_resident_bytes: int = 0, lib=None, bai_path: Optional[str] = None, index_tile_records: int = 0):
     """`ngs convert --gzip device --sort coordinate <BAM> <BAM>` in process (include/ngsq_bamsort.h): the records of the BAM at
     `path`, in any order, written to out_path (created or truncated) in coordinate order, unplaced ones last, inflated, sorted
     and compressed on GPU `device`.  max_records: the first so many records are sorted (0: all; the command line maps `-n N` to
     max(N, 1)); batch_records: records per ingest batch; piece_bytes: sorted record bytes gathered and compressed at a time;
     max_resident_bytes: device memory the records may take (0 each: the library's defaults).  Returns the report; NgsqError on
-    an open failure, a file the ingest refuses or records beyond the limits."""
+    an open failure, a file the ingest refuses or records beyond the limits.
+    bai_path: `--write-index` (ngsq_bam_write_sorted_bam_indexed): the BAI of out_path is written there, index_tile_records sorted
+    records per launch of the index pass (0: the library's default); returns (sort report, index report)."""
     lib = lib or ffi.load_library()
     with _reader_and_plain_context(lib, path, device, "opening BAM input file: ") as (bam, ctx):
         fd = os.open(out_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o666)
         try:
             rep = ffi.BamSortReport()
-            _check_bam(lib.ngsq_bam_write_sorted_bam(bam, ctx, fd, max_records, batch_records, piece_bytes, max_resident_bytes,
-                                                     C.byref(rep)), lib)
-            return {k: getattr(rep, k) for k, _ in ffi.BamSortReport._fields_}
+            if bai_path is None:
+                _check_bam(lib.ngsq_bam_write_sorted_bam(bam, ctx, fd, max_records, batch_records, piece_bytes, max_resident_bytes,
+                                                         C.byref(rep)), lib)
+                return {k: getattr(rep, k) for k, _ in ffi.BamSortReport._fields_}
+            irep = ffi.IndexReport()
+            _check_bam(lib.ngsq_bam_write_sorted_bam_indexed(bam, ctx, fd, max_records, batch_records, piece_bytes, max_resident_bytes,
+                                                             C.byref(rep), bai_path.encode(), index_tile_records, C.byref(irep)), lib)
+            return {k: getattr(rep, k) for k, _ in ffi.BamSortReport._fields_}, _index_report(irep, lib)
         finally:
             os.close(fd)
 
