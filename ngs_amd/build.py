@@ -27,7 +27,7 @@ HEADERS = ["kernels.h", "context.h", "comm.h", "mem_pool.h", "bam_reader.h", "in
            "derive_kernels.h", "../../include/ngsq_derive.h",
            "device_out.h", "sam_run.h", "view_kernels.h", "view_query.h", "../../include/ngsq_view.h",
            "generate_kernels.h", "generate_draw.h", "reference_load.h", "../../include/ngsq_generate.h",
-           "samtext_kernels.h", "samtext_host.h", "../../include/ngsq_samtext.h",
+           "samtext_kernels.h", "samtext_host.h", "samtext_run.h", "../../include/ngsq_samtext.h",
            "sort_kernels.h", "../../include/ngsq_sort.h", "sort_resident.h", "../../include/ngsq_bamsort.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-result", "-fno-gpu-rdc"]
 FLAGS += os.environ.get("NGSQ_EXTRA_FLAGS", "").split()  # extra compiler flags for a local build, e.g. -save-temps (use --force)

@@ -1,9 +1,9 @@
 // bamsort.cpp -- include/ngsq_bamsort.h: `ngs convert --gzip device --sort coordinate <BAM> <BAM>`.  Three
 // phases on one GPU.  (1) The batch walk of the device ingest that sam.cpp and bai.cpp use: the records of a batch are one byte
 // range of the ingest's view, k_sort_keep copies that range into a slab of device memory and leaves every record's address,
-// length and key behind.  (2) and (3) are sort_resident.h's, shared with samsort.cpp.  The whole input is walked before the
-// writer starts, so every fault of the file is known before the first byte is written.  The host reads two words per batch and
-// a few per piece and never walks a record.
+// length and key behind.  The admission of a batch to the slabs, phases (2) and (3) and the shared fields of the report are
+// sort_resident.h's, shared with samsort.cpp.  The whole input is walked before the writer starts, so every fault of the file is
+// known before the first byte is written.  The host reads two words per batch and a few per piece and never walks a record.
 #include "../../include/ngsq_bamsort.h"
 
 #include "ingest_consumer.h"
@@ -17,7 +17,7 @@ namespace {
 constexpr uint64_t BATCH_RECORDS = (uint64_t)1 << 22;
 constexpr const char *READ_CTX = "reading BAM record: ";
 
-// the ingest's message (or the shared phases') behind the context
+// the ingest's message behind the context
 int read_failed(int rc) {
     const std::string m = ngsq_bam_last_error();
     return ngsq_bam_fail(rc, "%s%s", READ_CTX, m.c_str());
@@ -46,31 +46,24 @@ int write_sorted(ngsq_bam *b, ngsq_ctx *c, int fd, uint64_t max_records, uint64_
     hs += sorted_text;
     hs += b->ref_table;
 
-    BHIP(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     HipEvents<2> ev; // around a batch's k_sort_keep
     MappedBuf span;  // where a batch's records lie in the view: two words the host reads
-    SortResident R;  // the slabs, the per-record arrays, phases 2 and 3
-    if (bai_path) {
-        R.ix.on = true;
-        R.ix.path = bai_path;
-        R.ix.ctx = READ_CTX;
-        R.ix.tile_records = index_tile_records;
-        R.ix.ref_lens = b->ref_lens; // the binary reference lengths
-    }
-    uint64_t batches = 0, budget = max_resident_bytes, slab_bytes = 0, view_bytes = 0;
+    SortResident R;  // the slabs, the per-record arrays, phases 2 and 3; behind `span`: its drain of st runs before the words go
+    if (bai_path) R.ix.enable(bai_path, READ_CTX, index_tile_records, b->ref_lens); // the binary reference lengths
+    R.budget = max_resident_bytes;
+    uint64_t batches = 0, slab_bytes = 0, view_bytes = 0;
     double scan_ms = 0, keep_ms = 0;
     bool keep_pending = false; // the last batch's bracket has not been added to keep_ms yet
-    auto shared_failed = [&](int rc) { return ngsq_bam_fail(rc, "%s", R.err.c_str()); };
     auto add_keep_time = [&]() {
         float ms = 0;
         if (keep_pending && hipEventElapsedTime(&ms, ev.e[0], ev.e[1]) == hipSuccess) keep_ms += ms;
         keep_pending = false;
     };
 
-    // phase 1: every batch's records copied into a slab, nothing compressed
+    // phase 1: every batch's records copied into a slab, nothing compressed.  (R's failures leave their message in R.err.)
     auto keep_all = [&]() -> int {
-        if (const int rc = R.begin(st)) return shared_failed(rc);
+        if (const int rc = R.begin(c->device, st)) return rc;
         for (auto &e : ev.e) BHIP(hipEventCreate(&e));
         BHIP(span.reserve(2 * sizeof(unsigned long long)));
         const unsigned long long *const sp = static_cast<const unsigned long long *>(span.h);
@@ -91,11 +84,8 @@ int write_sorted(ngsq_bam *b, ngsq_ctx *c, int fd, uint64_t max_records, uint64_
                 uint64_t chunk_bytes = 0;
                 bam_device_view_sizes(b, &chunk_bytes, &view_bytes);
                 slab_bytes = std::min(std::max(2 * chunk_bytes, SORT_SLAB_MIN), SORT_SLAB_MAX);
-                if (!budget) {
-                    size_t free_b = 0, total_b = 0;
-                    BHIP(hipMemGetInfo(&free_b, &total_b));
-                    budget = free_b > SORT_DEVICE_RESERVE ? free_b - SORT_DEVICE_RESERVE : 0;
-                }
+                if (!R.budget)
+                    if (const int brc = R.default_budget()) return brc;
             }
             // the batch's byte range in the view
             BHIP(launch_sort_span(o.raw, o.rec_off, n, static_cast<unsigned long long *>(span.dev), st));
@@ -105,15 +95,9 @@ int write_sorted(ngsq_bam *b, ngsq_ctx *c, int fd, uint64_t max_records, uint64_
                 return ngsq_bam_fail(NGSQ_ERR_STATE, "%sthe records of batch %llu lie at [%llu, %llu) of a view of %llu bytes", READ_CTX,
                                      (unsigned long long)batches, (unsigned long long)begin, (unsigned long long)end, (unsigned long long)view_bytes);
             const uint64_t bytes = end - begin;
-            if (R.records + n > 0xFFFFFFFFull) return ngsq_bam_fail(NGSQ_ERR_LIMIT, "%s--sort coordinate sorts at most 2^32 - 1 records", READ_CTX);
-            const uint64_t need = R.rec_bytes + bytes + (R.records + n) * SORT_BYTES_PER_RECORD;
-            if (need > budget)
-                return ngsq_bam_fail(NGSQ_ERR_LIMIT, "%s--sort coordinate holds the records in device memory: %llu bytes needed, %llu allowed", READ_CTX,
-                                     (unsigned long long)need, (unsigned long long)budget);
             // the records stay: behind the last batch's in the newest slab, at the source's residue modulo 16, or in a new slab
             uint8_t *dst = nullptr;
-            if (const int prc = R.place(bytes, slab_bytes, (uint32_t)((uintptr_t)(o.raw + begin) & 15u), &dst)) return shared_failed(prc);
-            if (const int prc = R.reserve_records(R.records + n)) return shared_failed(prc);
+            if (const int arc = R.admit(n, bytes, slab_bytes, (uint32_t)((uintptr_t)(o.raw + begin) & 15u), READ_CTX, &dst)) return arc;
             BHIP(hipEventRecord(ev.e[0], st));
             BHIP(launch_sort_keep(o.raw, o.rec_off, n, begin, bytes, dst, R.records, R.d_addr.p, R.d_len.p, R.d_key.p, st));
             BHIP(hipEventRecord(ev.e[1], st));
@@ -128,34 +112,19 @@ int write_sorted(ngsq_bam *b, ngsq_ctx *c, int fd, uint64_t max_records, uint64_
     };
 
     int rc = keep_all();
-    bool shared = false; // rc is the shared phases' and its message R.err
-    if (rc == NGSQ_OK) shared = (rc = R.sort_and_write(fd, c->device, hs, piece_bytes)) != NGSQ_OK;
-    const int before = rc;
+    if (rc == NGSQ_OK) rc = R.sort_and_write(fd, hs, piece_bytes);
     rc = R.finish(rc, fd);
-    if (rc != NGSQ_OK && (shared || before == NGSQ_OK)) shared_failed(rc);
+    if (rc != NGSQ_OK && !R.err.empty()) ngsq_bam_fail(rc, "%s", R.err.c_str());
     if (out) {
-        out->records = R.records;
+        R.report(out);
         out->header_bytes = sorted_text.size();
-        out->bam_bytes = R.bam_bytes;
-        out->compressed_bytes = R.enc.comp_bytes;
         out->batches = batches;
         out->slabs = R.slabs.size();
-        out->pieces = R.pieces;
-        out->blocks = R.enc.blocks;
-        out->stored_blocks = R.enc.stored;
-        out->resident_bytes = R.resident_bytes();
-        out->passes_run = R.sort.passes_run;
-        out->passes_skipped = SORT_DIGITS - R.sort.passes_run; // (no records: no pass, as ngsq_sort_u64_device reports it)
         out->scan_ms = scan_ms;
         out->keep_ms = keep_ms;
-        out->sort_ms = R.sort_ms;
-        out->gather_ms = R.gather_ms;
-        out->deflate_ms = R.deflate_ms;
-        out->d2h_ms = R.w.copy_ms;
-        out->write_ms = R.w.write_ms;
         out->total_ms = now_ms() - t_begin;
     }
-    if (bai_path) R.ix.report(R.records, index_out);
+    R.ix.report(R.records, index_out);
     return rc;
 }
 

@@ -1,7 +1,9 @@
 // device_out.h -- the output stage the commands that write a file share: a batch of output bytes
 // lies in a device buffer, and a writer thread copies it through a pinned ring to a file descriptor while the main thread
 // produces the next batch.  `ngs convert` and `ngs view` hand it SAM text (sam_run.h), `ngs generate` FASTQ text or BGZF blocks,
-// one writer per file (generate.cpp), SAM to BAM its BGZF blocks (samtext.cpp).  Nothing here knows what the bytes are.
+// one writer per file (generate.cpp).  The three commands that write one BAM file through the device encoder (samtext.cpp,
+// and samsort.cpp and bamsort.cpp through sort_resident.h) share BgzfSink at the end of this file: encoder, slots, writer and
+// the EOF block.  Nothing above it knows what the bytes are.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -272,6 +274,89 @@ struct BgzfEncoder {
         blocks += deflate_blocks(bytes);
         stored += h[DH_STORED];
         return nullptr;
+    }
+};
+
+// One BGZF file through the device encoder: the encoder with the words the host reads of it, the two slots of its block buffers,
+// the writer, the EOF block.  Per job: acquire() (waits until job k - 2 has been copied), fill the source, launch(), other
+// work, hand_over() (waits for the encoder).  The three stay apart so that each caller keeps its waits where its overlap
+// needs them.  A failure leaves its code and its message here; the caller reports it through its own channel.  The sink
+// drains nothing: whoever owns it drains the stream of launch() before the sink goes (the drain rule above).
+struct BgzfSink {
+    BgzfEncoder enc;
+    JobSlots slots;
+    MappedBuf hw;      // the encoder's words
+    HipEvents<1> done; // behind the encoder of the job in flight
+    hipStream_t st = nullptr;
+    DeviceWriter w; // (behind the encoder's buffers: it ends, and its copies with it, before they go)
+    uint64_t bam_bytes = 0; // the bytes handed over, before compression
+    double deflate_ms = 0;
+    int code = 0;
+    std::string err;
+
+    int fail(int code_, const std::string &m) {
+        err = m;
+        return code = code_;
+    }
+    int copy_failed(hipError_t e) { return fail(NGSQ_ERR_DEVICE, std::string("copying the BGZF blocks to the host: ") + hipGetErrorString(e)); }
+    int write_failed(int e) { return fail(NGSQ_ERR_INVALID_ARGUMENT, std::string("writing BAM record: ") + strerror(e) + " (os error " + std::to_string(e) + ")"); }
+#define ZHIP(expr)                                                                                              \
+    do {                                                                                                        \
+        hipError_t e_ = (expr);                                                                                 \
+        if (e_ != hipSuccess) return fail(NGSQ_ERR_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
+    } while (0)
+    // the words, the events, and the writer of fd on `device` (made current)
+    int start(int fd, int device) {
+        ZHIP(hipSetDevice(device));
+        ZHIP(hw.reserve(DEFLATE_HOST_WORDS * sizeof(unsigned long long)));
+        memset(hw.h, 0, DEFLATE_HOST_WORDS * sizeof(unsigned long long));
+        enc.h = static_cast<const unsigned long long *>(hw.h);
+        enc.hdev = static_cast<unsigned long long *>(hw.dev);
+        ZHIP(hipEventCreate(&done.e[0]));
+        ZHIP(slots.create());
+        ZHIP(w.start(fd, device));
+        return NGSQ_OK;
+    }
+    int acquire() { return slots.acquire(&w) ? NGSQ_OK : copy_failed(w.herr); }
+    // src[0, bytes) (device, DEFLATE_IN_SLACK readable bytes behind it) through the encoder into the buffer of the job's slot
+    int launch(const void *src, uint64_t bytes, hipStream_t stream) {
+        st = stream;
+        ZHIP(enc.launch(slots.slot(), src, bytes, st));
+        ZHIP(hipEventRecord(done.e[0], st));
+        return NGSQ_OK;
+    }
+    // The blocks of the job launched go to the writer once the encoder has ended; its time counts from `since`.  file_at
+    // (optional): where the job's first block lies in the file.
+    int hand_over(uint64_t bytes, hipEvent_t since, uint64_t *file_at = nullptr) {
+        ZHIP(hipEventSynchronize(done.e[0]));
+        if (file_at) *file_at = enc.comp_bytes;
+        const char *blocks = nullptr;
+        uint64_t n = 0;
+        if (const char *m = enc.collect(slots.slot(), bytes, &blocks, &n)) return fail(NGSQ_ERR_STATE, m);
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, since, done.e[0]) == hipSuccess) deflate_ms += ms;
+        // (nothing may be queued on st between launch and here: `ready` would cover it and hold the copy back)
+        ZHIP(slots.submit(w, blocks, n, st));
+        bam_bytes += bytes;
+        return NGSQ_OK;
+    }
+#undef ZHIP
+    // The writer ended: every job written, or skipped after a failed write.  Its errors are reported when nothing failed before
+    // them (rc), a failed copy before a failed write.
+    int stop(int rc) {
+        const WriterEnd end = w.end();
+        if (rc == NGSQ_OK && end.herr != hipSuccess) rc = copy_failed(end.herr);
+        if (rc == NGSQ_OK && end.werr) rc = write_failed(end.werr);
+        return rc;
+    }
+    // stop(), then the EOF block behind a file that is whole
+    int end(int rc, int fd) {
+        rc = stop(rc);
+        if (rc == NGSQ_OK) {
+            if (const int e = write_bgzf_eof(fd)) rc = write_failed(e);
+            enc.comp_bytes += sizeof BGZF_EOF_BLOCK;
+        }
+        return rc;
     }
 };
 

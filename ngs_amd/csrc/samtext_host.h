@@ -1,7 +1,7 @@
-// samtext_host.h -- the host side the two drivers of SAM to BAM share (DESIGN.md sections 18.2 and 19.2): samtext.cpp
-// (`ngs convert --gzip device`, records compressed as they are parsed) and samsort.cpp (`--sort coordinate`, records resident
-// until their order is known).  The header and its reference list, the header stream, the reference table for the device,
-// the reader that cuts the text into chunks, the words of the messages.
+// samtext_host.h -- the host-only pieces of SAM to BAM, which samtext_run.h puts together into the
+// chunk pipeline and the drivers (samtext.cpp, samsort.cpp; bamsort.cpp for the header text) use beside it: the header and its
+// reference list, the header stream, the reference table for the device, the reader that cuts the text into chunks, the words
+// of the messages.
 #pragma once
 
 #include <fcntl.h>
@@ -172,6 +172,7 @@ struct RefTable {
     std::string names;
     uint32_t slots = 1, n_refs = 0;
 
+    RefTable() = default;
     explicit RefTable(const SamHeader &H) : n_refs((uint32_t)H.names.size()) {
         while (slots < 2ull * n_refs) slots <<= 1;
         words.assign(1 + n_refs + 1 + (slots + 1) / 2, 0);

@@ -1,9 +1,10 @@
 // sort_resident.h -- what the two drivers of `ngs convert --sort coordinate` share (DESIGN.md sections 19.2 and 20.2): samsort.cpp
 // (SAM text in) and bamsort.cpp (BAM in).  A driver's phase 1 leaves the records in slabs of device memory and their addresses,
 // lengths and keys in the three per-record arrays; phases 2 and 3 are here: sort_pairs_u64 orders (key, record index) pairs, the
-// sorted stream is cut into pieces of piece_bytes, per piece k_sort_gather copies the records to their sorted offsets, the
-// device DEFLATE encoder makes BGZF blocks of them and the output stage of device_out.h writes them, behind the header's blocks
-// and in front of the EOF block.  A failure leaves its code and its message in `err`; the driver reports it through its own channel.
+// sorted stream is cut into pieces of piece_bytes, per piece k_sort_gather copies the records to their sorted offsets and the
+// sink of device_out.h compresses and writes them, behind the header's blocks and in front of the EOF block.  Also here, once
+// for both drivers: the admission of phase 1's records to the slabs (the limits, the default budget, the place) and the fields
+// their reports share.  A failure leaves its code and its message in `err`; the driver reports it through its own channel.
 // With `ix.on` (--write-index) the BAI of the file is built on the way: an index pass over the sorted order
 // before the writer starts, the encoder's block offsets kept per piece, and one translation from stream offsets to virtual
 // positions behind the last piece; bai.cpp's writer makes the file once the EOF block is out.
@@ -41,11 +42,11 @@ struct SortIndexSplit {
 };
 inline thread_local SortIndexSplit g_sort_index_split;
 
-// What --write-index adds to a SortResident.  The driver sets `on`, the path, the tile, the sequences' lengths and its message
-// prefix before sort_and_write; everything else is the shared phases'.
+// What --write-index adds to a SortResident.  The driver calls enable() before sort_and_write; everything else is the shared
+// phases'.
 struct SortIndex {
     bool on = false;
-    std::string path, ctx;       // <TO>.bai; "reading BAM record: " or "reading SAM record: "
+    std::string path, ctx;
     uint64_t tile_records = SORT_INDEX_TILE;
     std::vector<uint32_t> ref_lens;
     BaiTables T;
@@ -60,7 +61,17 @@ struct SortIndex {
     double write_ms = 0;
     BaiFileCounts counts;
 
+    // path_: <TO>.bai; ctx_: the driver's message prefix; tile: sorted records per tile of the index pass (0: SORT_INDEX_TILE);
+    // lens: the sequences' lengths
+    void enable(const char *path_, const char *ctx_, uint64_t tile, const std::vector<uint32_t> &lens) {
+        on = true;
+        path = path_;
+        ctx = ctx_;
+        tile_records = tile;
+        ref_lens = lens;
+    }
     void report(uint64_t records, ngsq_index_report *out) const {
+        if (!on) return;
         g_sort_index_split = ms;
         if (!out) return;
         out->records = records;
@@ -73,9 +84,9 @@ struct SortIndex {
 };
 
 struct SortResident {
-    enum Ev { EV_S0 = 0, EV_S1, EV_G0, EV_G1, EV_Z1, EV_I0, EV_I1, EV_B0, EV_B1, EV_N };
-    enum HostWord : uint32_t { HW_TOTAL = 0, HW_DEFLATE, HW_WORDS = HW_DEFLATE + DEFLATE_HOST_WORDS };
+    enum Ev { EV_S0 = 0, EV_S1, EV_G0, EV_G1, EV_I0, EV_I1, EV_B0, EV_B1, EV_N };
 
+    int device = 0;
     hipStream_t st = nullptr;
     // phase 1 fills these: record i of the input lies at d_addr[i], d_len[i] bytes, with the key d_key[i]
     DevArray<uint64_t> d_addr, d_key;
@@ -83,22 +94,23 @@ struct SortResident {
     std::vector<std::unique_ptr<DevArray<uint8_t>>> slabs; // the records: a slab is filled from its front and never moved
     uint64_t slab_used = 0;
     uint64_t records = 0, rec_bytes = 0;
+    uint64_t budget = 0; // what resident_bytes() may come to
     // phases 2 and 3
     DevArray<uint64_t> d_soff;
     DevArray<uint8_t> d_piece;
     ScanScratch scan;
     SortScratch sort;
-    BgzfEncoder enc; // d_piece's bytes become the blocks of a job
-    JobSlots zslots;
-    MappedBuf hw, hw_first;
+    BgzfSink z;               // d_piece's bytes become the blocks of a job
+    MappedBuf hw, hw_first; // the sorted stream's length; the record every piece begins in
     HipEvents<EV_N> ev;
-    DeviceWriter w;
-    uint64_t bam_bytes = 0, pieces = 0;
-    double sort_ms = 0, gather_ms = 0, deflate_ms = 0;
+    uint64_t pieces = 0;
+    double sort_ms = 0, gather_ms = 0;
     SortIndex ix;
     int code = 0;
     std::string err;
-    StreamDrain drain; // (behind the arrays: it runs first)
+    // The drain rule (device_out.h), behind everything above: the stream is idle before the slabs, the per-record arrays, the
+    // index's arrays and the sink's block buffers go.  A driver's own arrays go after this object or behind a drain of theirs.
+    StreamDrain drain;
 
     int fail(int code_, const char *fmt, ...) {
         char buf[1024];
@@ -115,22 +127,29 @@ struct SortResident {
         if (e_ != hipSuccess) return fail(NGSQ_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-    // the stream the drivers' kernels run on, the events, the words the host reads
-    int begin(hipStream_t stream) {
+    int sunk(int rc) { return rc ? fail(rc, "%s", z.err.c_str()) : rc; } // a step of the sink: its message becomes this object's
+
+    // the device (made current), the stream the drivers' kernels run on, the events, the word the host reads
+    int begin(int device_, hipStream_t stream) {
+        device = device_;
+        SRHIP(hipSetDevice(device));
         st = drain.s = stream;
-        SRHIP(hw.reserve(HW_WORDS * sizeof(unsigned long long)));
-        memset(hw.h, 0, HW_WORDS * sizeof(unsigned long long));
-        enc.h = static_cast<const unsigned long long *>(hw.h) + HW_DEFLATE;
-        enc.hdev = static_cast<unsigned long long *>(hw.dev) + HW_DEFLATE;
+        SRHIP(hw.reserve(sizeof(unsigned long long)));
+        memset(hw.h, 0, sizeof(unsigned long long));
         for (auto &e : ev.e) SRHIP(hipEventCreate(&e));
+        return NGSQ_OK;
+    }
+    // the budget of a call that names none: what is free on the device now, less SORT_DEVICE_RESERVE
+    int default_budget() {
+        size_t free_b = 0, total_b = 0;
+        SRHIP(hipMemGetInfo(&free_b, &total_b));
+        budget = free_b > SORT_DEVICE_RESERVE ? free_b - SORT_DEVICE_RESERVE : 0;
         return NGSQ_OK;
     }
     void elapsed(int a, int b, double *sum) {
         float ms = 0;
         if (hipEventElapsedTime(&ms, ev.e[a], ev.e[b]) == hipSuccess) *sum += ms;
     }
-    int copy_failed(hipError_t e) { return fail(NGSQ_ERR_DEVICE, "copying the BGZF blocks to the host: %s", hipGetErrorString(e)); }
-    int write_failed(int e) { return fail(NGSQ_ERR_INVALID_ARGUMENT, "writing BAM record: %s (os error %d)", strerror(e), e); }
 
     // Room for `bytes` more record bytes whose first lies at an address of residue `residue` modulo 16 (residue > 15: anywhere):
     // behind the newest slab's records, or at the front of a new slab of slab_bytes (or of what these records need).
@@ -153,6 +172,18 @@ struct SortResident {
         SRHIP(d_len.reserve_keep(n, st));
         SRHIP(d_key.reserve_keep(n, st));
         return NGSQ_OK;
+    }
+    // Phase 1 asks for n more records of `bytes` bytes (ctx: the driver's message prefix): refused beyond the sort's index
+    // width or the budget; else *dst is where they go (place) and the per-record arrays have room for them.  The driver
+    // queues what fills them and then adds n and bytes to `records` and `rec_bytes`.
+    int admit(uint64_t n, uint64_t bytes, uint64_t slab_bytes, uint32_t residue, const char *ctx, uint8_t **dst) {
+        if (records + n > 0xFFFFFFFFull) return fail(NGSQ_ERR_LIMIT, "%s--sort coordinate sorts at most 2^32 - 1 records", ctx);
+        const uint64_t need = rec_bytes + bytes + (records + n) * SORT_BYTES_PER_RECORD;
+        if (need > budget)
+            return fail(NGSQ_ERR_LIMIT, "%s--sort coordinate holds the records in device memory: %llu bytes needed, %llu allowed", ctx,
+                        (unsigned long long)need, (unsigned long long)budget);
+        if (const int rc = place(bytes, slab_bytes, residue, dst)) return rc;
+        return reserve_records(records + n);
     }
 
     // the time of the last append to the block table, once the stream has passed it
@@ -197,11 +228,11 @@ struct SortResident {
     }
 
     // Behind the last piece: the run starts and the filled windows become virtual positions through the block table, and come
-    // to the host.  (Every piece has been collected: enc.comp_bytes is where the EOF block will lie.)
+    // to the host.  (Every piece has been handed over: z.enc.comp_bytes is where the EOF block will lie.)
     int index_translate(uint64_t piece_bytes, uint64_t total) {
         BaiTables &T = ix.T;
         add_append_time();
-        const BaiBlocks B{ix.d_table.p, piece_bytes, ix.blocks_per_piece, total, enc.comp_bytes};
+        const BaiBlocks B{ix.d_table.p, piece_bytes, ix.blocks_per_piece, total, z.enc.comp_bytes};
         SRHIP(hipEventRecord(ev.e[EV_I0], st));
         SRHIP(launch_bai_translate(B, ix.d_runs.p, ix.runs, T.d_lin.p, T.n_win, st));
         SRHIP(hipEventRecord(ev.e[EV_I1], st));
@@ -211,26 +242,20 @@ struct SortResident {
         if (T.n_win) SRHIP(hipMemcpyAsync(ix.lin.data(), T.d_lin.p, T.n_win * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         SRHIP(hipStreamSynchronize(st));
         elapsed(EV_I0, EV_I1, &ix.ms.translate_ms);
-        ix.final_end = enc.comp_bytes << 16;
+        ix.final_end = z.enc.comp_bytes << 16;
         return NGSQ_OK;
     }
 
-    // bytes of d_piece through the encoder into its buffer of the job's slot, the blocks to the writer (as samtext.cpp's jobs);
-    // table (optional): the job's block offsets in the file go there, behind the hand-over
+    // bytes of d_piece, filled before EV_G1, through the sink (acquired by the caller); table (optional): the job's block
+    // offsets in the file go there, behind the hand-over.  (To run the encoder beside the next gather, part launch from
+    // hand_over here and give the pieces two buffers: DESIGN.md sections 19.5 and 20.5.)
     int compress_and_push(uint64_t bytes, uint64_t *table = nullptr) {
-        SRHIP(enc.launch(zslots.slot(), d_piece.p, bytes, st));
-        SRHIP(hipEventRecord(ev.e[EV_Z1], st));
-        SRHIP(hipEventSynchronize(ev.e[EV_Z1]));
+        uint64_t file_at = 0;
+        if (sunk(z.launch(d_piece.p, bytes, st)) || sunk(z.hand_over(bytes, ev.e[EV_G1], &file_at))) return code;
         add_append_time(); // (the last job's append lies in front of this encoder)
-        const char *blocks = nullptr;
-        uint64_t n = 0;
-        if (const char *m = enc.collect(zslots.slot(), bytes, &blocks, &n)) return fail(NGSQ_ERR_STATE, "%s", m);
-        elapsed(EV_G1, EV_Z1, &deflate_ms);
-        SRHIP(zslots.submit(w, blocks, n, st));
-        bam_bytes += bytes;
         if (table) {
             SRHIP(hipEventRecord(ev.e[EV_B0], st));
-            SRHIP(launch_bai_blocks(enc.sc.off.p, deflate_blocks(bytes), enc.comp_bytes - n, table, st));
+            SRHIP(launch_bai_blocks(z.enc.sc.off.p, deflate_blocks(bytes), file_at, table, st));
             SRHIP(hipEventRecord(ev.e[EV_B1], st));
             ix.append_pending = true;
         }
@@ -238,9 +263,7 @@ struct SortResident {
     }
 
     // phases 2 and 3: the order, then the header stream hs, then the pieces, to fd
-    int sort_and_write(int fd, int device, const std::string &hs, uint64_t piece_bytes) {
-        unsigned long long *const hdev = static_cast<unsigned long long *>(hw.dev);
-        const unsigned long long *const h = static_cast<const unsigned long long *>(hw.h);
+    int sort_and_write(int fd, const std::string &hs, uint64_t piece_bytes) {
         const uint32_t *perm = nullptr;
         uint64_t total = 0;
         const unsigned long long *first = nullptr;
@@ -251,11 +274,11 @@ struct SortResident {
             SRHIP(d_soff.reserve(records + 1));
             SRHIP(launch_sort_lengths(d_len.p, perm, records, d_soff.p, st));
             SRHIP(scan.exclusive_scan(d_soff.p, records + 1, st));
-            SRHIP(launch_samtext_word(d_soff.p, records, hdev + HW_TOTAL, st));
+            SRHIP(launch_samtext_word(d_soff.p, records, static_cast<unsigned long long *>(hw.dev), st));
             SRHIP(hipEventRecord(ev.e[EV_S1], st));
             SRHIP(hipStreamSynchronize(st));
             elapsed(EV_S0, EV_S1, &sort_ms);
-            total = h[HW_TOTAL];
+            total = *static_cast<const unsigned long long *>(hw.h);
             if (total != rec_bytes)
                 return fail(NGSQ_ERR_STATE, "the sorted records take %llu bytes, the parsed ones %llu", (unsigned long long)total, (unsigned long long)rec_bytes);
             pieces = (total + piece_bytes - 1) / piece_bytes;
@@ -270,18 +293,17 @@ struct SortResident {
             ix.blocks_per_piece = deflate_blocks(piece_bytes);
             SRHIP(ix.d_table.reserve(pieces * ix.blocks_per_piece + 1));
         }
-        SRHIP(zslots.create());
-        SRHIP(w.start(fd, device));
+        if (sunk(z.start(fd, device))) return code;
         // the header's blocks, in front of the first record (as samtools writes them)
         SRHIP(d_piece.reserve(std::max<uint64_t>(hs.size(), std::min(piece_bytes, total)) + DEFLATE_IN_SLACK));
         SRHIP(hipMemcpyAsync(d_piece.p, hs.data(), hs.size(), hipMemcpyHostToDevice, st));
         SRHIP(hipEventRecord(ev.e[EV_G1], st));
         if (const int rc = compress_and_push(hs.size())) return rc;
-        for (uint64_t j = 0; j < pieces && !w.failed(); j++) {
+        for (uint64_t j = 0; j < pieces && !z.w.failed(); j++) {
             const uint64_t lo = j * piece_bytes, hi = std::min(lo + piece_bytes, total);
             // records first[j] .. first[j + 1]: the last of them may begin in this piece and end in the next
             const uint64_t a = first[j], b = std::min<uint64_t>(first[j + 1] + 1, records);
-            if (!zslots.acquire(&w)) return copy_failed(w.herr);
+            if (sunk(z.acquire())) return code;
             SRHIP(hipEventRecord(ev.e[EV_G0], st));
             SRHIP(launch_sort_gather(d_addr.p, perm, d_soff.p, a, b, lo, hi, d_piece.p, st));
             SRHIP(hipEventRecord(ev.e[EV_G1], st));
@@ -289,22 +311,18 @@ struct SortResident {
             elapsed(EV_G0, EV_G1, &gather_ms);
         }
         SRHIP(hipStreamSynchronize(st));
-        if (ix.on && !w.failed())
+        if (ix.on && !z.w.failed())
             if (const int rc = index_translate(piece_bytes, total)) return rc;
         return NGSQ_OK;
     }
 #undef SRHIP
 
-    // The end of a call whose phases gave rc (a driver's own failure: this object's `err` is not set and stays so): the writer
-    // ended, its errors reported when nothing failed before them, the EOF block.
+    // The end of a call whose phases gave rc (a driver's own failure: this object's `err` is not set and stays so): the sink's
+    // end, then the index file.
     int finish(int rc, int fd) {
-        const WriterEnd end = w.end();
-        if (rc == NGSQ_OK && end.herr != hipSuccess) rc = copy_failed(end.herr);
-        if (rc == NGSQ_OK && end.werr) rc = write_failed(end.werr);
-        if (rc == NGSQ_OK) {
-            if (const int e = write_bgzf_eof(fd)) rc = write_failed(e);
-            enc.comp_bytes += sizeof BGZF_EOF_BLOCK;
-        }
+        const int before = rc;
+        rc = z.end(rc, fd);
+        if (rc != before) sunk(rc);
         // the index, once the file it describes is complete: beside its place and renamed (bai.cpp's writer)
         if (rc == NGSQ_OK && ix.on) {
             const double t0 = now_ms();
@@ -315,6 +333,23 @@ struct SortResident {
         return rc;
     }
     uint64_t resident_bytes() const { return rec_bytes + records * SORT_BYTES_PER_RECORD; }
+    // the fields the two drivers' reports share by name
+    template <class Report> void report(Report *out) const {
+        out->records = records;
+        out->bam_bytes = z.bam_bytes;
+        out->compressed_bytes = z.enc.comp_bytes;
+        out->pieces = pieces;
+        out->blocks = z.enc.blocks;
+        out->stored_blocks = z.enc.stored;
+        out->resident_bytes = resident_bytes();
+        out->passes_run = sort.passes_run;
+        out->passes_skipped = SORT_DIGITS - sort.passes_run; // (no records: no pass, as ngsq_sort_u64_device reports it)
+        out->sort_ms = sort_ms;
+        out->gather_ms = gather_ms;
+        out->deflate_ms = z.deflate_ms;
+        out->d2h_ms = z.w.copy_ms;
+        out->write_ms = z.w.write_ms;
+    }
 };
 
 } // namespace ngsq

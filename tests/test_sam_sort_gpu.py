@@ -183,6 +183,43 @@ def test_max_records_sorts_the_first_records_of_the_text(gpu_lib, ngs, tmp_path,
         assert gzip.decompress(open(tmp_path / "n.bam", "rb").read()) == som.bam_stream(sam, want)
 
 
+def test_chunk_edges_and_max_records_of_the_shared_parser(gpu_lib, tmp_path):
+    """The cases of test_chunk_edges and test_num_records_and_empty_files of tests/test_sam_to_bam_gpu.py through the sorted
+    path, which runs the same chunk parser: chunk ends on every byte of the lines, a line one byte longer than a chunk, a last
+    line without its newline, a fault in a later chunk, `max_records` on and beside the chunk ends."""
+    sam = shuffled(random_sam(43, 300, tmp_path), 88)
+    header, body = tm.split_header(sam)
+    lines = tm.body_lines(body)
+    longest = max(len(x) for x in lines)
+    want = som.bam_stream(sam)
+    for chunk in (longest, longest + 1, 1000):
+        _, rep, _ = check(gpu_lib, sam, tmp_path, want=want, chunk_bytes=chunk)
+        assert rep["chunks"] > 10 and rep["records"] == 300
+    with pytest.raises(host.NgsqError) as e:
+        convert(gpu_lib, sam, tmp_path, chunk_bytes=longest - 1)
+    k = next(i for i, x in enumerate(lines) if len(x) == longest)
+    assert e.value.message == f"reading SAM record: record {k}: line longer than {longest - 1} bytes"
+    assert os.path.getsize(tmp_path / "o.bam") == 0
+    check(gpu_lib, sam[:-1], tmp_path, chunk_bytes=1000)                          # a last line without its newline
+    # a faulty line in a chunk other than the first
+    good = ["\t".join(GOOD[:3] + [str(900 - k)] + GOOD[4:]) + "\n" for k in range(500)]
+    good[300] = line(f4="x")
+    with pytest.raises(host.NgsqError) as e:
+        convert(gpu_lib, (HEAD + "".join(good)).encode(), tmp_path, chunk_bytes=2000)
+    assert e.value.message == f"reading SAM record: record 300: {tm.ERROR_TEXT[tm.E_MAPQ]}"
+    assert os.path.getsize(tmp_path / "o.bam") == 0
+    # max_records; the records behind which the host cuts its chunks: up to chunk + 1 bytes from the last cut, cut at their last newline
+    chunk, ends, at = 2000, [], 0
+    while at < len(body):
+        at += body[at:at + chunk + 1].rfind(b"\n") + 1
+        ends.append(body[:at].count(b"\n"))
+    assert len(ends) > 10 and ends[-1] == 300 and ends[0] > 1
+    for n, chunks in ((1, 1), (ends[0] - 1, 1), (ends[0], 1), (ends[0] + 1, 2), (ends[4], 5), (ends[4] + 1, 6), (300, len(ends)), (10 ** 6, len(ends))):
+        _, rep, _ = check(gpu_lib, sam, tmp_path, max_records=n, chunk_bytes=chunk)
+        assert rep["records"] == min(n, 300) and rep["text_bytes"] == sum(len(x) + 1 for x in lines[:n])
+        assert rep["chunks"] == chunks, (n, rep["chunks"], chunks)               # (nothing is read or launched behind the last record)
+
+
 # ---- 5. refusals ------------------------------------------------------------------------------------------------------------
 def test_a_faulty_line_keeps_its_message_and_index(gpu_lib, tmp_path):
     good = ["\t".join(GOOD[:3] + [str(900 - k)] + GOOD[4:]) + "\n" for k in range(500)]
