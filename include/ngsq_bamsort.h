@@ -12,6 +12,7 @@
 #include "ngsq.h"
 #include "ngsq_bam.h"
 #include "ngsq_index.h"
+#include "ngsq_sort.h" /* ngsq_sort_survey_bytes_per_record, ngsq_sort_resident_bytes_per_record */
 
 #ifdef __cplusplus
 extern "C" {
@@ -60,6 +61,34 @@ int ngsq_bam_write_sorted_bam_indexed(ngsq_bam *bam, ngsq_ctx *ctx, int fd, uint
                                       uint64_t max_resident_bytes, ngsq_bamsort_report *out, const char *bai_path, uint64_t index_tile_records,
                                       ngsq_index_report *index_out);
 
+/* How ngsq_bam_write_sorted_bam_rounds went about a file. */
+typedef struct ngsq_bamsort_rounds {
+    uint64_t rounds;         /* ranges of the sorted order that were resident in turn (1: the records fitted the budget) */
+    uint64_t walks;          /* walks of the input begun: 1, or the attempt that overflowed, the survey and one per round */
+    uint64_t survey_records; /* records the survey walk saw (0: no survey) */
+    uint64_t survey_bytes;   /* what the survey's arrays were counted as: ngsq_sort_survey_bytes_per_record() per record */
+    uint64_t budget;         /* the budget in force: max_resident_bytes, or the default */
+    double survey_ms;        /* wall clock of the survey: its walk, its sort and the plan */
+} ngsq_bamsort_rounds;
+
+/* ngsq_bam_write_sorted_bam (bai_path null) or ngsq_bam_write_sorted_bam_indexed without the limit of max_resident_bytes: `ngs
+ * convert --gzip device --sort coordinate [--sort-memory <SIZE>] <BAM> <BAM>`.  Records that fit the budget:
+ * exactly the call above, one walk of the input, rounds = 1.  Records that do not: the attempt is dropped and the input walked
+ * again from its beginning -- a survey walk that keeps a key and a length per record (ngsq_sort_survey_bytes_per_record() bytes
+ * each, counted against the budget), sorts them and cuts the sorted order greedily into consecutive ranges of records whose bytes
+ * and ngsq_sort_resident_bytes_per_record() bytes each fit the budget; then one walk per range ("round") that keeps that range's
+ * records, sorts them and continues the file's stream of pieces.  The bytes written to fd, and to bai_path, are those of the calls
+ * above at a budget that fits, for the same input, max_records and piece_bytes.  NGSQ_ERR_LIMIT, before anything is written to
+ * fd: "reading BAM record: --sort coordinate in rounds holds a key per record in device memory: N bytes needed, M allowed" (the
+ * survey alone does not fit), "reading BAM record: record N (0-based) of the sorted output alone takes B bytes of device memory,
+ * M allowed" (one record does not), and with bai_path a record the BAI cannot hold, in the words and with the number of the call
+ * above.  NGSQ_ERR_STATE, "the input changed between walks: ...", when a round finds other records than the survey planned: the
+ * file was rewritten underneath the call, and what has been written to fd by then is no BAM.  `out` as above, with batches =
+ * the survey walk's, slabs and resident_bytes = the largest round's, passes_run and passes_skipped = the survey sort's, and
+ * the times summed over the walks and rounds.  rounds_out (optional) as above. */
+int ngsq_bam_write_sorted_bam_rounds(ngsq_bam *bam, ngsq_ctx *ctx, int fd, uint64_t max_records, uint64_t batch_records, uint64_t piece_bytes,
+                                     uint64_t max_resident_bytes, ngsq_bamsort_report *out, const char *bai_path, uint64_t index_tile_records,
+                                     ngsq_index_report *index_out, ngsq_bamsort_rounds *rounds_out);
 /* The device time the last indexed call on this thread (this one or ngsq_sam_write_sorted_bam_indexed) spent on its index, in
  * ms: the index pass, the appends to the block table, the translation to virtual positions.  Null pointers are skipped. */
 void ngsq_sort_index_split(double *pass_ms, double *blocks_ms, double *translate_ms);

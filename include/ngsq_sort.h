@@ -24,6 +24,11 @@ typedef struct ngsq_sort_report {
 int ngsq_sort_u64_device(int device, const uint64_t *keys, uint64_t n, uint32_t *perm, ngsq_sort_report *rep);
 /* keys one workgroup ranks at a time: tests place their edges by it */
 uint32_t ngsq_sort_tile_keys(void);
+/* Device bytes `ngs convert --sort coordinate` counts per record against its budget (ngsq_bamsort.h): beside a resident record's
+ * own bytes (address, length, key, the sort's arrays, the sorted offset: 48), and per record of the survey of a file sorted in
+ * rounds (key, length, the sort's arrays, its share of the pass table).  Tests and models read them here. */
+uint64_t ngsq_sort_resident_bytes_per_record(void);
+uint64_t ngsq_sort_survey_bytes_per_record(void);
 const char *ngsq_sort_last_error(void);
 
 #ifdef __cplusplus

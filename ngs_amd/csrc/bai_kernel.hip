@@ -84,13 +84,17 @@ struct RecRules {
     bool head, bad, limit, lin_w;
     uint32_t from;
 };
+// the BAI cannot hold this placed record
+__device__ inline bool bai_limit(const RecInfo &me, const BaiLinear &L) {
+    return (uint32_t)me.ref >= L.n_refs || me.end > BAI_MAX_POS || me.w1 >= L.lin_cap[me.ref];
+}
 __device__ inline RecRules bai_rec_rules(const RecInfo &me, const RecPrev &p, const BaiLinear &L) {
     RecRules r{false, false, false, false, 0};
     if (me.placed) {
         r.bad = p.has && (!p.placed || me.ref < p.ref || (me.ref == p.ref && me.pos < p.pos));
         r.head = !p.has || !p.placed || me.ref != p.ref || me.bin != p.bin;
         r.from = p.has && p.placed && p.ref == me.ref && p.w1 + 1 > me.w0 ? p.w1 + 1 : me.w0;
-        r.limit = (uint32_t)me.ref >= L.n_refs || me.end > BAI_MAX_POS || me.w1 >= L.lin_cap[me.ref];
+        r.limit = bai_limit(me, L);
     } else {
         r.head = !p.has || p.placed;
     }
@@ -224,11 +228,11 @@ __device__ inline uint64_t bai_span(const uint8_t *p, uint32_t n) {
     return span;
 }
 
-// Record k of the sorted order, read where phase 1 left it: block_size, refID, pos, l_read_name | mapq | bin, n_cigar_op | flag,
+// The record at p (any byte alignment), read where phase 1 left it or in the ingest's view: block_size, refID, pos, l_read_name | mapq | bin, n_cigar_op | flag,
 // l_seq are its first 24 bytes -- seven aligned words, shifted -- then the CIGAR, or the CG:B,I tag's operations behind the
-// placeholder (as k_rec_fixed resolves it).  The reads stay inside the record and the slab's slack (SORT_GATHER_SLACK).
-__device__ inline RecInfo bai_sorted_info(const BaiSorted &t, uint64_t k, uint32_t *flag) {
-    const uint8_t *p = reinterpret_cast<const uint8_t *>(t.addr[t.perm[k]]);
+// placeholder (as k_rec_fixed resolves it).  The reads stay inside the record and the slab's slack (SORT_GATHER_SLACK; the
+// view's buffer has more behind it).
+__device__ inline RecInfo bai_info_at(const uint8_t *p, uint32_t *flag) {
     const uint32_t *w = reinterpret_cast<const uint32_t *>((uintptr_t)p & ~(uintptr_t)3);
     const uint32_t sh = (uint32_t)((uintptr_t)p & 3u) * 8u;
     uint32_t a[7];
@@ -254,6 +258,22 @@ __device__ inline RecInfo bai_sorted_info(const BaiSorted &t, uint64_t k, uint32
     return bai_rec_info((int32_t)bai_shift(a[1], a[2], sh), (int32_t)bai_shift(a[2], a[3], sh), bai_span(cig, real_ops));
 }
 
+// record k of the sorted order
+__device__ inline RecInfo bai_sorted_info(const BaiSorted &t, uint64_t k, uint32_t *flag) {
+    return bai_info_at(reinterpret_cast<const uint8_t *>(t.addr[t.perm[k]]), flag);
+}
+
+// The survey of a BAM sorted in rounds: the limit test of bai_rec_rules on every record of a batch, in
+// input order, before any record is resident; a record that fails it gets the mark in its survey length.
+__global__ __launch_bounds__(BT) void k_bai_survey(const uint8_t *__restrict__ raw, const uint64_t *__restrict__ rec_off, uint64_t n, uint64_t first,
+                                                   BaiLinear L, uint32_t mark, uint32_t *__restrict__ len) {
+    const uint64_t i = (uint64_t)blockIdx.x * BT + threadIdx.x;
+    if (i >= n) return;
+    uint32_t flag = 0;
+    const RecInfo me = bai_info_at(raw + rec_off[i], &flag);
+    if (me.placed && bai_limit(me, L)) len[first + i] |= mark;
+}
+
 // One thread per record of the tile [first, first + n) of the sorted order.  A position is the record's offset in the sorted
 // stream plus one (0 stays "no record" for k_bai_finish's fill); k_bai_translate makes virtual positions of them.
 __global__ __launch_bounds__(BT) void k_bai_sorted(BaiSorted t, BaiState *__restrict__ st, uint32_t parity, BaiLinear L,
@@ -269,11 +289,11 @@ __global__ __launch_bounds__(BT) void k_bai_sorted(BaiSorted t, BaiState *__rest
     RecRules r{};
     if (act) r = bai_rec_rules(me, p, L);
     uint64_t startv = 0;
-    if (r.head || r.lin_w) startv = t.soff[t.first + i] + 1;
-    bai_apply(act, me, r, flag, i, t.first + i, startv, st, L, run_flag, tmp);
+    if (r.head || r.lin_w) startv = t.pos0 + t.soff[t.first + i] + 1;
+    bai_apply(act, me, r, flag, i, t.rec0 + t.first + i, startv, st, L, run_flag, tmp);
     if (act && i == t.n - 1) {
         run_flag[t.n] = 0;
-        st->carry[parity ^ 1u] = bai_carry_of(me, t.soff[t.first + i + 1] + 1);
+        st->carry[parity ^ 1u] = bai_carry_of(me, t.pos0 + t.soff[t.first + i + 1] + 1);
     }
 }
 
@@ -377,6 +397,15 @@ hipError_t launch_bai_sorted(const BaiSorted &t, BaiState *state, uint32_t parit
     const uint64_t blocks = (t.n + BT - 1) / BT;
     if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_bai_sorted, dim3((uint32_t)blocks), dim3(BT), 0, s, t, state, parity, lin, run_flag, tmp_runs);
+    return hipGetLastError();
+}
+
+hipError_t launch_bai_survey(const uint8_t *raw, const uint64_t *rec_off, uint64_t n, uint64_t first, const BaiLinear &lin, uint32_t mark,
+                             uint32_t *len, hipStream_t s) {
+    if (!n) return hipSuccess;
+    const uint64_t blocks = (n + BT - 1) / BT;
+    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_bai_survey, dim3((uint32_t)blocks), dim3(BT), 0, s, raw, rec_off, n, first, lin, mark, len);
     return hipGetLastError();
 }
 

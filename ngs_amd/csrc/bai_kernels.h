@@ -65,11 +65,16 @@ struct BaiSorted {
     const uint32_t *perm;
     const uint64_t *soff;
     uint64_t first, n;
+    uint64_t rec0, pos0; // what lies in front of soff[0]: records and bytes of the sorted stream (a file sorted in rounds; else 0)
 };
 // launch_bai_records for such a tile.  The positions it leaves (run starts, windows, the carry's endv) are stream offsets plus
 // one, so that k_bai_finish's 0 keeps meaning "no record in front"; BaiRun::rec is the index in the sorted order.
 hipError_t launch_bai_sorted(const BaiSorted &t, BaiState *state, uint32_t parity, const BaiLinear &lin, uint64_t *run_flag, BaiRun *tmp_runs,
                              hipStream_t s);
+// A batch of the device ingest, record i at raw + rec_off[i], before anything is resident (a BAM sorted in rounds, DESIGN.md
+// section 22.3): len[first + i] gets `mark` where launch_bai_sorted would refuse the record as one the BAI cannot hold.
+hipError_t launch_bai_survey(const uint8_t *raw, const uint64_t *rec_off, uint64_t n, uint64_t first, const BaiLinear &lin, uint32_t mark,
+                             uint32_t *len, hipStream_t s);
 // The file's BGZF blocks that hold records: piece j of piece_bytes stream bytes is blocks [j * blocks_per_piece, ...) of coff,
 // DEFLATE_BLOCK_INPUT stream bytes each, coff their file offsets; the stream has `total` bytes and the EOF block lies at eof_coff.
 struct BaiBlocks {

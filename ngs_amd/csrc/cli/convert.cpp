@@ -4,7 +4,8 @@
 // (include/ngsq_samtext.h); with the additive `--sort coordinate` beside it the records are sorted there too
 // (ngsq_sam_write_sorted_bam); and with both flags BAM to sorted BAM (ngsq_bam_write_sorted_bam,
 // include/ngsq_bamsort.h); with the additive `--write-index` beside those two the BAI of the sorted BAM is
-// written with it.  Without the flags every command line answers as a build without that direction.
+// written with it; a BAM whose records do not fit the device's memory, or the additive `--sort-memory`,
+// is sorted in rounds (ngsq_bam_write_sorted_bam_rounds).  Without the flags every command line answers as a build without that direction.
 #include <fcntl.h>
 #include <sys/stat.h>
 
@@ -24,6 +25,8 @@ struct ConvertArgs {
     bool gzip_device = false;              // --gzip device: SAM to BAM is converted, its BGZF written on the GPU
     bool sort_coordinate = false;          // --sort coordinate: ... and its records sorted there
     bool write_index = false;              // --write-index: ... and <TO>.bai written beside the sorted BAM
+    bool has_sort_memory = false;          // --sort-memory: what the resident records may take of device memory
+    unsigned long long sort_memory = 0;
     unsigned long long n = 0;
     int device = 0;
 };
@@ -58,7 +61,11 @@ bool parse_args(int argc, char **argv, int at, ConvertArgs *a) {
                     "          any record order to a sorted one [default: none] [possible values: none, coordinate]\n"
                     "      --write-index\n"
                     "          With --gzip device and --sort coordinate (additive, this build): write the index <TO>.bai beside the sorted\n"
-                    "          BAM, the file `ngs index <TO>` would write, built on the GPU while the BAM is written\n\n"
+                    "          BAM, the file `ngs index <TO>` would write, built on the GPU while the BAM is written\n"
+                    "      --sort-memory <SIZE>\n"
+                    "          With --gzip device and --sort coordinate (additive, this build): device memory the records being sorted may\n"
+                    "          take, in bytes or with a K, M or G suffix; a BAM beyond it is sorted in rounds, each a walk of the input that\n"
+                    "          keeps one range of the sorted order [default: the free memory of the device, less 4 GiB]\n\n"
                     "This build converts BAM to SAM, and with --gzip device SAM to BAM: the text is parsed and the BGZF blocks are\n"
                     "written on the GPU, whose encoder has one setting (-c is checked and takes no part).  With --gzip device and\n"
                     "--sort coordinate it also converts BAM to BAM: the file is inflated, sorted and compressed on the GPU.\n");
@@ -92,6 +99,24 @@ bool parse_args(int argc, char **argv, int at, ConvertArgs *a) {
             else bail("invalid value '" + v + "' for '--sort <ORDER>' [possible values: none, coordinate]");
         } else if (s == "--write-index") {
             a->write_index = true;
+        } else if (s == "--sort-memory") {
+            // decimal digits with an optional K, M or G, powers of 1024 (as `samtools sort -m` reads its value)
+            const std::string v = val("--sort-memory <SIZE>");
+            const std::string what = "invalid value '" + v + "' for '--sort-memory <SIZE>': ";
+            size_t d = 0;
+            while (d < v.size() && v[d] >= '0' && v[d] <= '9') d++;
+            if (!d) bail(what + "a size is decimal digits with an optional K, M or G suffix");
+            unsigned shift = 0;
+            if (d + 1 == v.size() && (v[d] == 'K' || v[d] == 'k')) shift = 10;
+            else if (d + 1 == v.size() && (v[d] == 'M' || v[d] == 'm')) shift = 20;
+            else if (d + 1 == v.size() && (v[d] == 'G' || v[d] == 'g')) shift = 30;
+            else if (d != v.size()) bail(what + "a size is decimal digits with an optional K, M or G suffix");
+            errno = 0;
+            const unsigned long long digits = strtoull(v.substr(0, d).c_str(), nullptr, 10);
+            if (errno || digits > (~0ull >> shift)) bail(what + "number too large to fit in target type");
+            if (!digits) bail(what + "a size is at least one byte");
+            a->sort_memory = digits << shift;
+            a->has_sort_memory = true;
         } else if (!s.empty() && s[0] == '-' && s != "-") bail("unexpected argument '" + s + "' found");
         else a->pos.push_back(s);
     }
@@ -137,8 +162,9 @@ int sam_to_bam(const ConvertArgs &a, const std::string &from, const std::string 
     ngsq_samtext_report rep{};
     ngsq_samsort_report srep{};
     ngsq_index_report irep{};
-    const int rc = a.write_index       ? ngsq_sam_write_sorted_bam_indexed(ctx, from.c_str(), fd, max_records, 0, 0, 0, &srep, bai.c_str(), 0, &irep)
-                   : a.sort_coordinate ? ngsq_sam_write_sorted_bam(ctx, from.c_str(), fd, max_records, 0, 0, 0, &srep)
+    // (--sort-memory is the budget and nothing else here: SAM input stays in memory)
+    const int rc = a.write_index       ? ngsq_sam_write_sorted_bam_indexed(ctx, from.c_str(), fd, max_records, 0, 0, a.sort_memory, &srep, bai.c_str(), 0, &irep)
+                   : a.sort_coordinate ? ngsq_sam_write_sorted_bam(ctx, from.c_str(), fd, max_records, 0, 0, a.sort_memory, &srep)
                                        : ngsq_sam_write_bam(ctx, from.c_str(), fd, max_records, 0, &rep);
     const std::string msg = rc ? ngsq_last_error(ctx) : "";
     const int close_rc = close(fd), close_errno = errno;
@@ -194,8 +220,8 @@ int bam_to_sorted_bam(const ConvertArgs &a, const std::string &from, const std::
     const uint64_t max_records = a.has_n ? std::max<unsigned long long>(a.n, 1) : 0;
     ngsq_bamsort_report rep{};
     ngsq_index_report irep{};
-    const int rc = a.write_index ? ngsq_bam_write_sorted_bam_indexed(bam, ctx, fd, max_records, 0, 0, 0, &rep, bai.c_str(), 0, &irep)
-                                 : ngsq_bam_write_sorted_bam(bam, ctx, fd, max_records, 0, 0, 0, &rep);
+    ngsq_bamsort_rounds rrep{};
+    const int rc = ngsq_bam_write_sorted_bam_rounds(bam, ctx, fd, max_records, 0, 0, a.sort_memory, &rep, a.write_index ? bai.c_str() : nullptr, 0, &irep, &rrep);
     const std::string msg = rc ? ngsq_bam_last_error() : "";
     const int close_rc = close(fd), close_errno = errno;
     ngsq_destroy(ctx);
@@ -211,6 +237,10 @@ int bam_to_sorted_bam(const ConvertArgs &a, const std::string &from, const std::
                 (unsigned long long)rep.header_bytes, (unsigned long long)rep.bam_bytes, (unsigned long long)rep.pieces, (unsigned long long)rep.blocks,
                 (unsigned long long)rep.stored_blocks, (unsigned long long)rep.compressed_bytes, rep.scan_ms, rep.keep_ms, rep.sort_ms, rep.gather_ms,
                 rep.deflate_ms, rep.d2h_ms, rep.write_ms, rep.total_ms);
+    if (g_level >= 3 && rrep.rounds > 1)
+        fprintf(stderr, "[ngs] convert: %llu rounds over %llu walks of the input, budget %llu bytes, survey %llu bytes in %.1f ms\n",
+                (unsigned long long)rrep.rounds, (unsigned long long)rrep.walks, (unsigned long long)rrep.budget, (unsigned long long)rrep.survey_bytes,
+                rrep.survey_ms);
     if (a.write_index) log_index_report(irep);
     return 0;
 }
@@ -239,6 +269,8 @@ int convert_main(int argc, char **argv, int at) {
     // (additive) the index is written where a sorted path is reached; refused before any file is opened
     if (a.write_index && !(a.gzip_device && a.sort_coordinate && tf == "BAM" && (ff == "SAM" || ff == "BAM")))
         bail("--write-index needs --gzip device and --sort coordinate and a BAM to write");
+    if (a.has_sort_memory && !(a.gzip_device && a.sort_coordinate && tf == "BAM" && (ff == "SAM" || ff == "BAM")))
+        bail("--sort-memory needs --gzip device and --sort coordinate and a BAM to write");
     if (ff == "SAM" && tf == "BAM" && a.gzip_device) return sam_to_bam(a, from, to);
     if (ff == "BAM" && tf == "BAM" && a.gzip_device && a.sort_coordinate) return bam_to_sorted_bam(a, from, to);
     if (reference_only)

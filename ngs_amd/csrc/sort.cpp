@@ -79,6 +79,8 @@ hipError_t sort_pairs_u64(uint64_t *keys, uint64_t n, SortScratch &sc, hipStream
 extern "C" {
 
 uint32_t ngsq_sort_tile_keys(void) { return SORT_TILE; }
+uint64_t ngsq_sort_resident_bytes_per_record(void) { return SORT_BYTES_PER_RECORD; }
+uint64_t ngsq_sort_survey_bytes_per_record(void) { return SORT_SURVEY_BYTES_PER_RECORD; }
 const char *ngsq_sort_last_error(void) { return g_sort_err.c_str(); }
 
 int ngsq_sort_u64_device(int device, const uint64_t *keys, uint64_t n, uint32_t *perm, ngsq_sort_report *rep) {

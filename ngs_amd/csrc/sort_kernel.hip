@@ -1,6 +1,7 @@
 // sort_kernel.hip -- the kernels of `ngs convert --sort coordinate`, gfx950, wave64: record keys, a
 // stable LSD radix sort of (key, index) pairs, and the gather of resident records into pieces of the sorted stream; for BAM input
-// (section 20.3) the copy of a batch of the device ingest into a slab.
+// (section 20.3) the copy of a batch of the device ingest into a slab; for a BAM sorted in rounds (section 22.3) the survey's keys,
+// the plan's cut and the copy of a round's records out of a batch.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -175,11 +176,11 @@ __global__ __launch_bounds__(BT) void k_sort_lengths(const uint32_t *__restrict_
     if (i == 0) slen[n] = 0;
 }
 
-__global__ __launch_bounds__(BT) void k_sort_bisect(const uint64_t *__restrict__ soff, uint64_t n, uint64_t piece_bytes, uint64_t pieces,
-                                                    unsigned long long *host) {
+__global__ __launch_bounds__(BT) void k_sort_bisect(const uint64_t *__restrict__ soff, uint64_t n, uint64_t piece_bytes, uint64_t first_piece,
+                                                    uint64_t before, uint64_t pieces, unsigned long long *host) {
     const uint64_t j = (uint64_t)blockIdx.x * BT + threadIdx.x;
     if (j > pieces) return;
-    const uint64_t target = j * piece_bytes;
+    const uint64_t at = (first_piece + j) * piece_bytes, target = at > before ? at - before : 0;
     uint64_t lo = 0, hi = n; // the smallest i with soff[i + 1] > target, n when there is none
     while (lo < hi) {
         const uint64_t mid = lo + (hi - lo) / 2;
@@ -217,6 +218,113 @@ __global__ __launch_bounds__(BT) void k_sort_gather(const uint64_t *__restrict__
     }
     const uint64_t tail = left & 7u;
     if (lane < tail) dst[words * 8 + lane] = src[words * 8 + lane];
+}
+
+// ---- rounds: the survey walk keeps a key and a length per record, a round's walk keeps the records
+// whose (key, input ordinal) lies inside the round's two boundaries
+
+__device__ __forceinline__ uint64_t key_of(const uint8_t *p) {
+    const int32_t ref_id = (int32_t)load_u32(p + 4), pos = (int32_t)load_u32(p + 8);
+    const uint32_t hi = (ref_id < 0 || pos < 0) ? 0xFFFFFFFFu : (uint32_t)ref_id, lo = (uint32_t)pos + 1u;
+    return (uint64_t)hi << 32 | lo;
+}
+
+__global__ __launch_bounds__(BT) void k_sort_survey(const uint8_t *__restrict__ raw, const uint64_t *__restrict__ rec_off, uint64_t n, uint64_t first,
+                                                    uint32_t *__restrict__ len, uint64_t *__restrict__ key) {
+    const uint64_t i = (uint64_t)blockIdx.x * BT + threadIdx.x;
+    if (i >= n) return;
+    const uint8_t *p = raw + rec_off[i];
+    len[first + i] = 4u + load_u32(p);
+    key[first + i] = key_of(p);
+}
+
+// the sorted lengths without the mark in their top bit, and the smallest sorted rank that carries it
+__global__ __launch_bounds__(BT) void k_sort_survey_lengths(const uint32_t *__restrict__ len, const uint32_t *__restrict__ perm, uint64_t n,
+                                                            uint64_t *__restrict__ slen, unsigned long long *__restrict__ marked) {
+    const uint64_t i = (uint64_t)blockIdx.x * BT + threadIdx.x;
+    if (i < n) {
+        const uint32_t l = len[perm[i]];
+        slen[i] = l & ~SORT_SURVEY_MARK;
+        if (l & SORT_SURVEY_MARK) (void)atomicMin(marked, (unsigned long long)i);
+    }
+    if (i == 0) slen[n] = 0;
+}
+
+// the largest end with soff[end] - soff[start] + per_record * (end - start) <= budget, and the boundary in front of it
+__global__ __launch_bounds__(64) void k_sort_plan(const uint64_t *__restrict__ soff, const uint64_t *__restrict__ skey, const uint32_t *__restrict__ perm,
+                                                  uint64_t n, uint64_t start, uint64_t budget, uint64_t per_record, unsigned long long *host) {
+    if (blockIdx.x || threadIdx.x) return;
+    uint64_t lo = start, hi = n;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo + 1) / 2;
+        if (soff[mid] - soff[start] + per_record * (mid - start) <= budget) lo = mid;
+        else hi = mid - 1;
+    }
+    host[SP_END] = lo;
+    host[SP_END_OFF] = soff[lo];
+    host[SP_KEY] = lo < n ? skey[lo] : ~0ull;
+    host[SP_ORD] = lo < n ? perm[lo] : ~0ull;
+    host[SP_FIRST_LEN] = start < n ? soff[start + 1] - soff[start] : 0;
+}
+
+__global__ __launch_bounds__(BT) void k_sort_round_flag(const uint8_t *__restrict__ raw, const uint64_t *__restrict__ rec_off, uint64_t n, uint64_t first,
+                                                        SortBound lo, SortBound hi, uint64_t *__restrict__ cnt, uint64_t *__restrict__ bytes) {
+    const uint64_t i = (uint64_t)blockIdx.x * BT + threadIdx.x;
+    if (i == 0) cnt[n] = bytes[n] = 0;
+    if (i >= n) return;
+    const uint8_t *p = raw + rec_off[i];
+    const uint64_t k = key_of(p), ord = first + i;
+    const bool in = (k > lo.key || (k == lo.key && ord >= lo.ord)) && (k < hi.key || (k == hi.key && ord < hi.ord));
+    cnt[i] = in ? 1 : 0;
+    bytes[i] = in ? 4u + (uint64_t)load_u32(p) : 0;
+}
+
+// A wave per record of the batch; a kept one goes whole to dst + off[r] and leaves address, length and key at first + cnt[r].
+// Source and destination lie at any byte offset: up to seven bytes until the destination is aligned, eight-byte stores of the
+// source's aligned words, shifted, and the rest by bytes.  The first word's low bytes come by bytes and the last word is left
+// to the tail, so that no load reaches in front of the record or behind it.
+__global__ __launch_bounds__(BT) void k_sort_take(const uint8_t *__restrict__ raw, const uint64_t *__restrict__ rec_off, uint64_t n,
+                                                  const uint64_t *__restrict__ cnt, const uint64_t *__restrict__ off, uint8_t *__restrict__ out,
+                                                  uint64_t first, uint64_t *__restrict__ addr, uint32_t *__restrict__ len, uint64_t *__restrict__ key) {
+    const uint64_t r = (uint64_t)blockIdx.x * GATHER_WAVES + (threadIdx.x >> 6);
+    if (r >= n) return;
+    const uint64_t c = cnt[r];
+    if (cnt[r + 1] == c) return;
+    const uint32_t lane = lane_id();
+    const uint8_t *src = raw + rec_off[r];
+    uint8_t *dst = out + off[r];
+    uint64_t left = off[r + 1] - off[r];
+    if (lane == 0) {
+        addr[first + c] = (uint64_t)(uintptr_t)dst;
+        len[first + c] = (uint32_t)left;
+        key[first + c] = key_of(src);
+    }
+    uint64_t head = (8u - (uint32_t)((uintptr_t)dst & 7u)) & 7u;
+    if (head > left) head = left;
+    if (lane < head) dst[lane] = src[lane];
+    src += head, dst += head, left -= head;
+    const uint32_t mis = (uint32_t)((uintptr_t)src & 7u), sh = mis * 8u;
+    uint64_t words = left >> 3;
+    if (mis && words) words--; // (its second source word would reach behind the record)
+    const uint64_t *sw = reinterpret_cast<const uint64_t *>(src - mis);
+    uint64_t *dw = reinterpret_cast<uint64_t *>(dst);
+    for (uint64_t k = lane; k < words; k += 64) {
+        uint64_t x;
+        if (!mis) {
+            x = sw[k];
+        } else {
+            uint64_t low = 0;
+            if (k == 0) { // (the aligned word begins in front of the record)
+                for (uint32_t q = 0; q < 8u - mis; q++) low |= (uint64_t)src[q] << (8u * (mis + q));
+            } else {
+                low = sw[k];
+            }
+            x = low >> sh | sw[k + 1] << (64u - sh);
+        }
+        dw[k] = x;
+    }
+    const uint64_t done = words * 8, tail = left - done; // (at most 15)
+    if (lane < tail) dst[done + lane] = src[done + lane];
 }
 
 uint32_t blocks_of(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
@@ -283,9 +391,46 @@ hipError_t launch_sort_lengths(const uint32_t *len, const uint32_t *perm, uint64
     return hipGetLastError();
 }
 
-hipError_t launch_sort_bisect(const uint64_t *soff, uint64_t n, uint64_t piece_bytes, uint64_t pieces, unsigned long long *host, hipStream_t s) {
+hipError_t launch_sort_bisect(const uint64_t *soff, uint64_t n, uint64_t piece_bytes, uint64_t first_piece, uint64_t before, uint64_t pieces,
+                              unsigned long long *host, hipStream_t s) {
     if (!piece_bytes || pieces >= 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_sort_bisect, dim3(blocks_of(pieces + 1, BT)), dim3(BT), 0, s, soff, n, piece_bytes, pieces, host);
+    hipLaunchKernelGGL(k_sort_bisect, dim3(blocks_of(pieces + 1, BT)), dim3(BT), 0, s, soff, n, piece_bytes, first_piece, before, pieces, host);
+    return hipGetLastError();
+}
+
+hipError_t launch_sort_survey(const uint8_t *raw, const uint64_t *rec_off, uint64_t n, uint64_t first, uint32_t *len, uint64_t *key, hipStream_t s) {
+    if (!n) return hipSuccess;
+    if (n > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_sort_survey, dim3(blocks_of(n, BT)), dim3(BT), 0, s, raw, rec_off, n, first, len, key);
+    return hipGetLastError();
+}
+
+hipError_t launch_sort_survey_lengths(const uint32_t *len, const uint32_t *perm, uint64_t n, uint64_t *slen, unsigned long long *marked, hipStream_t s) {
+    if (!n || n > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    const hipError_t e = hipMemsetAsync(marked, 0xFF, sizeof(unsigned long long), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_sort_survey_lengths, dim3(blocks_of(n, BT)), dim3(BT), 0, s, len, perm, n, slen, marked);
+    return hipGetLastError();
+}
+
+hipError_t launch_sort_plan(const uint64_t *soff, const uint64_t *skey, const uint32_t *perm, uint64_t n, uint64_t start, uint64_t budget,
+                            uint64_t per_record, unsigned long long *host, hipStream_t s) {
+    if (!n || start >= n) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_sort_plan, dim3(1), dim3(64), 0, s, soff, skey, perm, n, start, budget, per_record, host);
+    return hipGetLastError();
+}
+
+hipError_t launch_sort_round_flag(const uint8_t *raw, const uint64_t *rec_off, uint64_t n, uint64_t first, SortBound lo, SortBound hi, uint64_t *cnt,
+                                  uint64_t *bytes, hipStream_t s) {
+    if (!n || n > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_sort_round_flag, dim3(blocks_of(n, BT)), dim3(BT), 0, s, raw, rec_off, n, first, lo, hi, cnt, bytes);
+    return hipGetLastError();
+}
+
+hipError_t launch_sort_take(const uint8_t *raw, const uint64_t *rec_off, uint64_t n, const uint64_t *cnt, const uint64_t *off, uint8_t *dst,
+                            uint64_t first, uint64_t *addr, uint32_t *len, uint64_t *key, hipStream_t s) {
+    if (!n || n > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_sort_take, dim3(blocks_of(n, GATHER_WAVES)), dim3(BT), 0, s, raw, rec_off, n, cnt, off, dst, first, addr, len, key);
     return hipGetLastError();
 }
 

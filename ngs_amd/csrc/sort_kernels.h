@@ -48,13 +48,49 @@ hipError_t launch_sort_keep(const uint8_t *raw, const uint64_t *rec_off, uint64_
                             uint64_t *addr, uint32_t *len, uint64_t *key, hipStream_t s);
 // slen[i] = len[perm[i]], slen[n] = 0 (then scanned in place by the caller into the sorted offsets)
 hipError_t launch_sort_lengths(const uint32_t *len, const uint32_t *perm, uint64_t n, uint64_t *slen, hipStream_t s);
-// after the scan: host[j] (pinned, device address), j <= pieces, = the first record with a byte at or behind j * piece_bytes
-// of the sorted stream (n: none)
-hipError_t launch_sort_bisect(const uint64_t *soff, uint64_t n, uint64_t piece_bytes, uint64_t pieces, unsigned long long *host, hipStream_t s);
+// after the scan: host[j] (pinned, device address), j <= pieces, = the first record with a byte at or behind byte
+// (first_piece + j) * piece_bytes of the whole sorted stream (n: none); soff counts from `before` bytes into that stream
+hipError_t launch_sort_bisect(const uint64_t *soff, uint64_t n, uint64_t piece_bytes, uint64_t first_piece, uint64_t before, uint64_t pieces,
+                              unsigned long long *host, hipStream_t s);
 // The bytes [lo, hi) of the sorted stream to out[0, hi - lo): records [a, b) of the sorted order, each clipped to the range.
 // A wave per record; eight-byte stores behind an alignment prologue, the source read as whole words and shifted.
 hipError_t launch_sort_gather(const uint64_t *addr, const uint32_t *perm, const uint64_t *soff, uint64_t a, uint64_t b, uint64_t lo, uint64_t hi,
                               uint8_t *out, hipStream_t s);
+
+// Device bytes per resident record beside its own: address 8, length 4, key 8, the sort's second key array and its two index
+// arrays 16, the sorted offset 8, and its share of the pass table (half a byte).
+constexpr uint64_t SORT_BYTES_PER_RECORD = 48;
+
+// ---- a BAM sorted in rounds (bamsort.cpp drives these)
+
+// Device bytes per record of the survey: key 8, length 4, the sort's second key array 8 and its two index arrays 8, and its
+// share of the pass table (256 entries of 8 bytes per tile of SORT_TILE keys), rounded up.  The sorted offsets take no array of
+// their own: behind the sort they lie in the half of the key ping-pong that does not hold the sorted keys.
+constexpr uint64_t SORT_SURVEY_BYTES_PER_RECORD = 8 + 4 + 8 + 4 + 4 + (SORT_BINS * 8 + SORT_TILE - 1) / SORT_TILE;
+constexpr uint32_t SORT_SURVEY_MARK = 0x80000000u; // the top bit of a survey length (a record is shorter than 2^25 bytes): bai_kernel.hip sets it
+// a place in the sorted order: rank order is the order of (key, input ordinal) pairs, the sort being stable
+struct SortBound {
+    uint64_t key, ord;
+};
+enum { SP_END = 0, SP_END_OFF, SP_KEY, SP_ORD, SP_FIRST_LEN, SP_WORDS };
+// The records of a batch of the device ingest, record i at raw + rec_off[i]: the record of input ordinal first + i gets its
+// length 4 + block_size and launch_sort_keys' key.  No record byte and no address is kept.
+hipError_t launch_sort_survey(const uint8_t *raw, const uint64_t *rec_off, uint64_t n, uint64_t first, uint32_t *len, uint64_t *key, hipStream_t s);
+// launch_sort_lengths for survey lengths: slen drops SORT_SURVEY_MARK, *marked (device) = the smallest i whose length has it, ~0: none
+hipError_t launch_sort_survey_lengths(const uint32_t *len, const uint32_t *perm, uint64_t n, uint64_t *slen, unsigned long long *marked, hipStream_t s);
+// A round that begins at sorted rank start < n: host[SP_END] (pinned, device address) = the largest end whose records take
+// soff[end] - soff[start] + per_record * (end - start) <= budget, [SP_END_OFF] = soff[end], [SP_KEY], [SP_ORD] = the sorted key
+// and the input ordinal at rank end (~0 both: end == n), [SP_FIRST_LEN] = the length of the record at rank start.
+hipError_t launch_sort_plan(const uint64_t *soff, const uint64_t *skey, const uint32_t *perm, uint64_t n, uint64_t start, uint64_t budget,
+                            uint64_t per_record, unsigned long long *host, hipStream_t s);
+// cnt[i] = 1 and bytes[i] = its length where lo <= (key, first + i) < hi for record i of the batch, else 0 both; cnt[n] = bytes[n] = 0
+// (then scanned in place by the caller)
+hipError_t launch_sort_round_flag(const uint8_t *raw, const uint64_t *rec_off, uint64_t n, uint64_t first, SortBound lo, SortBound hi, uint64_t *cnt,
+                                  uint64_t *bytes, hipStream_t s);
+// after the two scans: every kept record whole to dst + off[i], compacted; record first + cnt[i] gets its address there, its
+// length and its key.  A wave per record; nothing outside a record or its place is read or written.
+hipError_t launch_sort_take(const uint8_t *raw, const uint64_t *rec_off, uint64_t n, const uint64_t *cnt, const uint64_t *off, uint8_t *dst,
+                            uint64_t first, uint64_t *addr, uint32_t *len, uint64_t *key, hipStream_t s);
 
 // the device arrays of a sort, beside the caller's keys: the ping-pong's other half, the pass table, the histograms
 struct SortScratch {

@@ -8,6 +8,8 @@
 // With `ix.on` (--write-index) the BAI of the file is built on the way: an index pass over the sorted order
 // before the writer starts, the encoder's block offsets kept per piece, and one translation from stream offsets to virtual
 // positions behind the last piece; bai.cpp's writer makes the file once the EOF block is out.
+// Phases 2 and 3 come in steps -- the file's beginning, a round, the file's end -- so that bamsort.cpp can sort a BAM beyond the
+// budget in rounds: each round's records are resident in turn and continue the same stream of pieces.
 #pragma once
 
 #include <cstdarg>
@@ -24,9 +26,6 @@
 namespace ngsq {
 
 constexpr uint64_t SORT_PIECE_DEFAULT = (uint64_t)64 << 20, SORT_PIECE_MAX = (uint64_t)1 << 30;
-// Device bytes per resident record beside its own: address 8, length 4, key 8, the sort's second key array and its two index
-// arrays 16, the sorted offset 8, and its share of the pass table (half a byte).
-constexpr uint64_t SORT_BYTES_PER_RECORD = 48;
 // What the default budget leaves free of the memory hipMemGetInfo reports: the two text buffers, a chunk's line and offset
 // arrays, the piece buffer, the encoder's scratch and its two block buffers, the unused end of the last slab, and the old
 // halves of the per-record arrays while they double.
@@ -54,7 +53,8 @@ struct SortIndex {
     DevArray<BaiRun> d_tmp, d_runs;     // a tile's tentative runs; the run list
     ScanScratch scan;
     uint64_t runs = 0, blocks_per_piece = 0, final_end = 0;
-    bool append_pending = false;
+    uint32_t parity = 0; // of the tile carry
+    bool begun = false, append_pending = false;
     std::vector<BaiRun> R; // what the end copies to the host: the run list and the windows, translated
     std::vector<unsigned long long> lin;
     SortIndexSplit ms;
@@ -104,6 +104,10 @@ struct SortResident {
     MappedBuf hw, hw_first; // the sorted stream's length; the record every piece begins in
     HipEvents<EV_N> ev;
     uint64_t pieces = 0;
+    // the file's sorted stream: its length, the piece size, and what the rounds written so far hold of it (bytes, records)
+    uint64_t total = 0, piece_bytes = 0, stream_at = 0, rank_at = 0;
+    const uint32_t *perm = nullptr; // order(): the resident records' sorted order
+    bool over_budget = false;       // admit() refused for the budget
     double sort_ms = 0, gather_ms = 0;
     SortIndex ix;
     int code = 0;
@@ -179,7 +183,7 @@ struct SortResident {
     int admit(uint64_t n, uint64_t bytes, uint64_t slab_bytes, uint32_t residue, const char *ctx, uint8_t **dst) {
         if (records + n > 0xFFFFFFFFull) return fail(NGSQ_ERR_LIMIT, "%s--sort coordinate sorts at most 2^32 - 1 records", ctx);
         const uint64_t need = rec_bytes + bytes + (records + n) * SORT_BYTES_PER_RECORD;
-        if (need > budget)
+        if ((over_budget = need > budget))
             return fail(NGSQ_ERR_LIMIT, "%s--sort coordinate holds the records in device memory: %llu bytes needed, %llu allowed", ctx,
                         (unsigned long long)need, (unsigned long long)budget);
         if (const int rc = place(bytes, slab_bytes, residue, dst)) return rc;
@@ -193,28 +197,44 @@ struct SortResident {
     }
 
     // The index pass: tiles of the sorted order through k_bai_sorted, the scan and the gather, the carry
-    // from tile to tile, then k_bai_finish.  Positions are offsets in the sorted stream plus one.  A record the BAI cannot hold
-    // is refused here, before the writer starts.
-    int index_pass(const uint32_t *perm) {
+    // from tile to tile, then k_bai_finish.  Positions are offsets in the sorted stream plus one.  In three steps, so that a file
+    // sorted in rounds (section 22.3) runs the tiles of every round between one beginning and one end: the tables, the carry and
+    // the run list stay from round to round.
+    int index_begin() {
+        if (ix.begun) return NGSQ_OK;
+        SRHIP(ix.T.create(ix.ref_lens.data(), (uint32_t)ix.ref_lens.size(), 1, st));
+        ix.begun = true;
+        return NGSQ_OK;
+    }
+    // the resident records in the order perm, behind rank_at records and stream_at bytes of the sorted stream
+    int index_tiles() {
         BaiTables &T = ix.T;
         SRHIP(hipEventRecord(ev.e[EV_I0], st));
-        SRHIP(T.create(ix.ref_lens.data(), (uint32_t)ix.ref_lens.size(), 1, st));
+        if (const int rc = index_begin()) return rc;
         const uint64_t tile = ix.tile_records ? ix.tile_records : SORT_INDEX_TILE;
-        uint32_t parity = 0;
         for (uint64_t k0 = 0; k0 < records; k0 += tile) {
             const uint64_t n = std::min(tile, records - k0);
             SRHIP(ix.d_flag.reserve(n + 1));
             SRHIP(ix.d_tmp.reserve(n));
             SRHIP(ix.d_runs.reserve_keep(ix.runs + n, st));
-            const BaiSorted t{d_addr.p, perm, d_soff.p, k0, n};
-            SRHIP(launch_bai_sorted(t, T.d_state, parity, T.L, ix.d_flag.p, ix.d_tmp.p, st));
+            const BaiSorted t{d_addr.p, perm, d_soff.p, k0, n, rank_at, stream_at};
+            SRHIP(launch_bai_sorted(t, T.d_state, ix.parity, T.L, ix.d_flag.p, ix.d_tmp.p, st));
             SRHIP(ix.scan.exclusive_scan(ix.d_flag.p, n + 1, st));
             SRHIP(launch_bai_gather(ix.d_flag.p, ix.d_tmp.p, n, ix.d_runs.p, ix.runs, T.host_count, st));
             SRHIP(hipStreamSynchronize(st)); // (the run list grows by what the tile gave it)
             ix.runs = T.pin_h[0];
-            parity ^= 1u;
+            ix.parity ^= 1u;
         }
-        SRHIP(launch_bai_finish(T.L, T.d_state, parity, T.host_fin, st));
+        SRHIP(hipEventRecord(ev.e[EV_I1], st));
+        SRHIP(hipStreamSynchronize(st));
+        elapsed(EV_I0, EV_I1, &ix.ms.pass_ms);
+        return NGSQ_OK;
+    }
+    // behind the last tile.  A record the BAI cannot hold is refused here; for a file in one round, before the writer starts.
+    int index_end() {
+        BaiTables &T = ix.T;
+        SRHIP(hipEventRecord(ev.e[EV_I0], st));
+        SRHIP(launch_bai_finish(T.L, T.d_state, ix.parity, T.host_fin, st));
         SRHIP(hipEventRecord(ev.e[EV_I1], st));
         SRHIP(hipStreamSynchronize(st));
         elapsed(EV_I0, EV_I1, &ix.ms.pass_ms);
@@ -222,9 +242,11 @@ struct SortResident {
         // (the order check of `ngs index`, kept as a check of the sort itself)
         if (fin[0] != ~0ull)
             return fail(NGSQ_ERR_STATE, "%srecord %llu (0-based) of the sorted output is out of coordinate order", ix.ctx.c_str(), fin[0]);
-        if (fin[1] != ~0ull)
-            return fail(NGSQ_ERR_LIMIT, "%srecord %llu (0-based) of the sorted output %s", ix.ctx.c_str(), fin[1], BAI_LIMIT_TEXT);
+        if (fin[1] != ~0ull) return limit_refused(fin[1]);
         return NGSQ_OK;
+    }
+    int limit_refused(uint64_t rank) {
+        return fail(NGSQ_ERR_LIMIT, "%srecord %llu (0-based) of the sorted output %s", ix.ctx.c_str(), (unsigned long long)rank, BAI_LIMIT_TEXT);
     }
 
     // Behind the last piece: the run starts and the filled windows become virtual positions through the block table, and come
@@ -262,15 +284,16 @@ struct SortResident {
         return NGSQ_OK;
     }
 
-    // phases 2 and 3: the order, then the header stream hs, then the pieces, to fd
-    int sort_and_write(int fd, const std::string &hs, uint64_t piece_bytes) {
-        const uint32_t *perm = nullptr;
-        uint64_t total = 0;
-        const unsigned long long *first = nullptr;
+    // Phases 2 and 3 in steps.  order() and write_round() are a round's: the records resident now are
+    // the next rec_bytes bytes of the file's sorted stream.  write_begin() and write_end() are the file's.  A file in one round is
+    // sort_and_write below; bamsort.cpp's rounds begin the file once the survey knows its length, then run round after round.
+
+    // the order of the resident records and their offsets behind stream_at; with the index on, its tiles over them
+    int order() {
+        perm = nullptr;
         if (records) {
             SRHIP(hipEventRecord(ev.e[EV_S0], st));
             SRHIP(sort_pairs_u64(d_key.p, records, sort, st, &perm));
-            // the sorted offsets, and the record every piece begins in
             SRHIP(d_soff.reserve(records + 1));
             SRHIP(launch_sort_lengths(d_len.p, perm, records, d_soff.p, st));
             SRHIP(scan.exclusive_scan(d_soff.p, records + 1, st));
@@ -278,18 +301,19 @@ struct SortResident {
             SRHIP(hipEventRecord(ev.e[EV_S1], st));
             SRHIP(hipStreamSynchronize(st));
             elapsed(EV_S0, EV_S1, &sort_ms);
-            total = *static_cast<const unsigned long long *>(hw.h);
-            if (total != rec_bytes)
-                return fail(NGSQ_ERR_STATE, "the sorted records take %llu bytes, the parsed ones %llu", (unsigned long long)total, (unsigned long long)rec_bytes);
-            pieces = (total + piece_bytes - 1) / piece_bytes;
-            if (pieces >= 0x7FFFFFFFull) return fail(NGSQ_ERR_LIMIT, "writing BAM record: more than 2^31 - 2 pieces of %llu bytes", (unsigned long long)piece_bytes);
-            SRHIP(hw_first.reserve((pieces + 1) * sizeof(unsigned long long)));
-            SRHIP(launch_sort_bisect(d_soff.p, records, piece_bytes, pieces, static_cast<unsigned long long *>(hw_first.dev), st));
-            SRHIP(hipStreamSynchronize(st));
-            first = static_cast<const unsigned long long *>(hw_first.h);
+            const uint64_t sorted = *static_cast<const unsigned long long *>(hw.h);
+            if (sorted != rec_bytes)
+                return fail(NGSQ_ERR_STATE, "the sorted records take %llu bytes, the parsed ones %llu", (unsigned long long)sorted, (unsigned long long)rec_bytes);
         }
+        return ix.on ? index_tiles() : NGSQ_OK;
+    }
+    // the writer, and the header stream hs in front of a sorted stream of `stream_bytes` bytes cut into pieces of piece_bytes_
+    int write_begin(int fd, const std::string &hs, uint64_t piece_bytes_, uint64_t stream_bytes) {
+        piece_bytes = piece_bytes_;
+        total = stream_bytes;
+        pieces = (total + piece_bytes - 1) / piece_bytes;
+        if (pieces >= 0x7FFFFFFFull) return fail(NGSQ_ERR_LIMIT, "writing BAM record: more than 2^31 - 2 pieces of %llu bytes", (unsigned long long)piece_bytes);
         if (ix.on) {
-            if (const int rc = index_pass(perm)) return rc;
             ix.blocks_per_piece = deflate_blocks(piece_bytes);
             SRHIP(ix.d_table.reserve(pieces * ix.blocks_per_piece + 1));
         }
@@ -298,22 +322,66 @@ struct SortResident {
         SRHIP(d_piece.reserve(std::max<uint64_t>(hs.size(), std::min(piece_bytes, total)) + DEFLATE_IN_SLACK));
         SRHIP(hipMemcpyAsync(d_piece.p, hs.data(), hs.size(), hipMemcpyHostToDevice, st));
         SRHIP(hipEventRecord(ev.e[EV_G1], st));
-        if (const int rc = compress_and_push(hs.size())) return rc;
-        for (uint64_t j = 0; j < pieces && !z.w.failed(); j++) {
+        return compress_and_push(hs.size());
+    }
+    // The resident records to their places in the pieces.  Piece j is bytes [j * piece_bytes, (j + 1) * piece_bytes) of the file's
+    // sorted stream, whatever round they come from: a piece this round leaves partly filled stays in d_piece, the next round's
+    // gather continues behind it, and it is compressed when it is full or the stream ends.
+    int write_round() {
+        if (!records) return NGSQ_OK;
+        const uint64_t begin = stream_at, end = begin + rec_bytes;
+        if (end > total) return fail(NGSQ_ERR_STATE, "the rounds' records take more than the %llu bytes of the sorted stream", (unsigned long long)total);
+        const uint64_t j0 = begin / piece_bytes, j1 = (end + piece_bytes - 1) / piece_bytes;
+        SRHIP(hw_first.reserve((j1 - j0 + 1) * sizeof(unsigned long long)));
+        SRHIP(launch_sort_bisect(d_soff.p, records, piece_bytes, j0, begin, j1 - j0, static_cast<unsigned long long *>(hw_first.dev), st));
+        SRHIP(hipStreamSynchronize(st));
+        const unsigned long long *first = static_cast<const unsigned long long *>(hw_first.h); // the record every piece begins in
+        for (uint64_t j = j0; j < j1 && !z.w.failed(); j++) {
             const uint64_t lo = j * piece_bytes, hi = std::min(lo + piece_bytes, total);
+            const uint64_t glo = std::max(lo, begin), ghi = std::min(hi, end); // what this round has of the piece
             // records first[j] .. first[j + 1]: the last of them may begin in this piece and end in the next
-            const uint64_t a = first[j], b = std::min<uint64_t>(first[j + 1] + 1, records);
+            const uint64_t a = first[j - j0], b = std::min<uint64_t>(first[j - j0 + 1] + 1, records);
             if (sunk(z.acquire())) return code;
             SRHIP(hipEventRecord(ev.e[EV_G0], st));
-            SRHIP(launch_sort_gather(d_addr.p, perm, d_soff.p, a, b, lo, hi, d_piece.p, st));
+            SRHIP(launch_sort_gather(d_addr.p, perm, d_soff.p, a, b, glo - begin, ghi - begin, d_piece.p + (glo - lo), st));
             SRHIP(hipEventRecord(ev.e[EV_G1], st));
-            if (const int rc = compress_and_push(hi - lo, ix.on ? ix.d_table.p + j * ix.blocks_per_piece : nullptr)) return rc;
+            if (ghi == hi) {
+                if (const int rc = compress_and_push(hi - lo, ix.on ? ix.d_table.p + j * ix.blocks_per_piece : nullptr)) return rc;
+            } else {
+                SRHIP(hipStreamSynchronize(st)); // (the piece waits for the next round's records)
+            }
             elapsed(EV_G0, EV_G1, &gather_ms);
         }
+        stream_at = end;
+        rank_at += records;
+        return NGSQ_OK;
+    }
+    // behind the last round: with the index on, the translation
+    int write_end() {
         SRHIP(hipStreamSynchronize(st));
+        if (!z.w.failed() && stream_at != total)
+            return fail(NGSQ_ERR_STATE, "the rounds' records take %llu bytes of a sorted stream of %llu", (unsigned long long)stream_at, (unsigned long long)total);
         if (ix.on && !z.w.failed())
             if (const int rc = index_translate(piece_bytes, total)) return rc;
         return NGSQ_OK;
+    }
+    // the records of a round are written: the slabs go, the per-record arrays stay for the next round's
+    int round_reset() {
+        SRHIP(hipStreamSynchronize(st));
+        slabs.clear();
+        slab_used = 0;
+        records = rec_bytes = 0;
+        return NGSQ_OK;
+    }
+
+    // phases 2 and 3 of a file in one round: the order, then the header stream hs, then the pieces, to fd
+    int sort_and_write(int fd, const std::string &hs, uint64_t piece_bytes_) {
+        if (const int rc = order()) return rc;
+        if (ix.on)
+            if (const int rc = index_end()) return rc;
+        if (const int rc = write_begin(fd, hs, piece_bytes_, rec_bytes)) return rc;
+        if (const int rc = write_round()) return rc;
+        return write_end();
     }
 #undef SRHIP
 
@@ -326,7 +394,7 @@ struct SortResident {
         // the index, once the file it describes is complete: beside its place and renamed (bai.cpp's writer)
         if (rc == NGSQ_OK && ix.on) {
             const double t0 = now_ms();
-            const std::string m = bai_write_file(ix.path.c_str(), ix.T, ix.R, ix.lin, records, ix.final_end, &ix.counts);
+            const std::string m = bai_write_file(ix.path.c_str(), ix.T, ix.R, ix.lin, rank_at, ix.final_end, &ix.counts);
             ix.write_ms = now_ms() - t0;
             if (!m.empty()) rc = fail(NGSQ_ERR_INVALID_ARGUMENT, "%s", m.c_str());
         }

@@ -262,6 +262,11 @@ class BamSortReport(C.Structure):
                 ("deflate_ms", C.c_double), ("d2h_ms", C.c_double), ("write_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class BamSortRounds(C.Structure):
+    _fields_ = [("rounds", C.c_uint64), ("walks", C.c_uint64), ("survey_records", C.c_uint64), ("survey_bytes", C.c_uint64),
+                ("budget", C.c_uint64), ("survey_ms", C.c_double)]
+
+
 # ---- include/ngsq_sort.h ----------------------------------------------------------------------
 class SortReport(C.Structure):
     _fields_ = [("passes_run", C.c_uint32), ("passes_skipped", C.c_uint32), ("sort_ms", C.c_double), ("total_ms", C.c_double)]
@@ -489,10 +494,14 @@ PROTOTYPES = {
     "ngsq_bam_write_sorted_bam": (C.c_int, [C.c_void_p, ctx_p, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(BamSortReport)]),
     "ngsq_bam_write_sorted_bam_indexed": (C.c_int, [C.c_void_p, ctx_p, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(BamSortReport),
                                                     C.c_char_p, C.c_uint64, C.POINTER(IndexReport)]),
+    "ngsq_bam_write_sorted_bam_rounds": (C.c_int, [C.c_void_p, ctx_p, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(BamSortReport),
+                                                   C.c_char_p, C.c_uint64, C.POINTER(IndexReport), C.POINTER(BamSortRounds)]),
     "ngsq_sort_index_split": (None, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     # include/ngsq_sort.h
     "ngsq_sort_u64_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(SortReport)]),
     "ngsq_sort_tile_keys": (C.c_uint32, []),
+    "ngsq_sort_resident_bytes_per_record": (C.c_uint64, []),
+    "ngsq_sort_survey_bytes_per_record": (C.c_uint64, []),
     "ngsq_sort_last_error": (C.c_char_p, []),
     # include/ngsq_view.h
     "ngsq_bam_query_chunks": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, u32p, u64p, u64p, C.POINTER(ViewChunk), C.c_uint64, u64p]),

@@ -633,7 +633,8 @@ def sam_to_sorted_bam(path: str, out_path: str, device: int = 0, max_records: in
 
 
 def bam_to_sorted_bam(path: str, out_path: str, device: int = 0, max_records: int = 0, batch_records: int = 0, piece_bytes: int = 0,
-                      max_resident_bytes: int = 0, lib=None, bai_path: Optional[str] = None, index_tile_records: int = 0):
+                      max_resident_bytes: int = 0, lib=None, bai_path: Optional[str] = None, index_tile_records: int = 0,
+                      rounds: bool = False):
     """`ngs convert --gzip device --sort coordinate <BAM> <BAM>` in process (include/ngsq_bamsort.h): the records of the BAM at
     `path`, in any order, written to out_path (created or truncated) in coordinate order, unplaced ones last, inflated, sorted
     and compressed on GPU `device`.  max_records: the first so many records are sorted (0: all; the command line maps `-n N` to
@@ -641,12 +642,24 @@ def bam_to_sorted_bam(path: str, out_path: str, device: int = 0, max_records: in
     max_resident_bytes: device memory the records may take (0 each: the library's defaults).  Returns the report; NgsqError on
     an open failure, a file the ingest refuses or records beyond the limits.
     bai_path: `--write-index` (ngsq_bam_write_sorted_bam_indexed): the BAI of out_path is written there, index_tile_records sorted
-    records per launch of the index pass (0: the library's default); returns (sort report, index report)."""
+    records per launch of the index pass (0: the library's default); returns (sort report, index report).
+    rounds: ngsq_bam_write_sorted_bam_rounds -- records beyond max_resident_bytes are no refusal: the input is walked again and
+    sorted in rounds, to the same bytes; returns (sort report, rounds report), or (sort report, index report, rounds report)."""
     lib = lib or ffi.load_library()
     with _reader_and_plain_context(lib, path, device, "opening BAM input file: ") as (bam, ctx):
         fd = os.open(out_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o666)
         try:
             rep = ffi.BamSortReport()
+            if rounds:
+                irep, rrep = ffi.IndexReport(), ffi.BamSortRounds()
+                _check_bam(lib.ngsq_bam_write_sorted_bam_rounds(bam, ctx, fd, max_records, batch_records, piece_bytes, max_resident_bytes,
+                                                                C.byref(rep), None if bai_path is None else bai_path.encode(),
+                                                                index_tile_records, C.byref(irep), C.byref(rrep)), lib)
+                sort_report = {k: getattr(rep, k) for k, _ in ffi.BamSortReport._fields_}
+                rounds_report = {k: getattr(rrep, k) for k, _ in ffi.BamSortRounds._fields_}
+                if bai_path is None:
+                    return sort_report, rounds_report
+                return sort_report, _index_report(irep, lib), rounds_report
             if bai_path is None:
                 _check_bam(lib.ngsq_bam_write_sorted_bam(bam, ctx, fd, max_records, batch_records, piece_bytes, max_resident_bytes,
                                                          C.byref(rep)), lib)
