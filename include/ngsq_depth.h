@@ -1,0 +1,86 @@
+/*
+ * ngsq_depth.h -- `ngs depth <BAM> [QUERY]`: the per-base depth of a coordinate-sorted BAM file, or of one region of it, as
+ * bedGraph text.  The records are read by the device ingest (one walk of the file, or the range walks of a region through the
+ * BAI, ngsq_view.h), turned into a difference array of the current sequence on the GPU, and each finished sequence is scanned,
+ * run-length coded and formatted there, tile by tile.  The reference has no such command: every rule
+ * below is this build's own decision, and tests/depth_model.py restates it.
+ *
+ * Which records count.  A record counts iff ref_id >= 0, pos >= 0, (flag & exclude_flags) == 0 and mapq >= min_mapq (a mapq of
+ * 255, "missing", counts as the number it is).  Its span is the reference bases of its resolved CIGAR -- M, D, N, = and X; a
+ * long CIGAR's operations come from CG:B,I, as both readers resolve it -- and must be at least 1: a record without a span
+ * covers nothing (the one-base rule of `ngs view` and `ngs index` is about finding records, not about covering bases).  It covers
+ * the 0-based positions [pos, min(pos + span, L)), L the sequence's length in the binary reference list: alignment start to
+ * alignment end, deletions and skips included (the reference's Coverage rule).  A record that starts at or
+ * beyond L covers nothing.
+ *
+ * What is written.  Lines "<name>\t<start>\t<end>\t<depth>\n": a 0-based half-open interval in decimal, <name> the bytes of
+ * the binary reference list.  The lines are the maximal runs of equal depth, zero included, and tile the axis exactly.
+ * Without a query every sequence of the header appears, in header order, tiled from 0 to L; a sequence without a counted
+ * record is the one line "name\t0\tL\t0"; a sequence of length 0 gives no line; a file without records tiles every sequence
+ * with zeros.  With a query ("name", "name:S", "name:S-E", the grammar of ngsq_bam_query_chunks) the one interval
+ * [S-1, min(E, L)) of that sequence is tiled: the first run starts at S-1, the last ends at min(E, L); an empty interval gives
+ * no line and is no error.  The records of a query are those of `ngs view`'s walks: the ones whose virtual offset lies in a
+ * merged chunk of the index.  The bytes depend on the file, the query and the two filters alone: not on batch_records,
+ * tile_positions, coalesce_gap or the grid.
+ *
+ * Order.  The header must say SO:coordinate (ngsq_bam_sorted_by_coordinate), else NGSQ_ERR_UNSORTED, "the input BAM must be
+ * coordinate-sorted to compute depth", before any GPU work.  A record out of order met on the walk -- the key of `ngs index`:
+ * (sequence, position), records without a sequence or a position last -- gives NGSQ_ERR_UNSORTED, "reading BAM record: record N
+ * (0-based) is out of coordinate order: the input BAM must be coordinate-sorted to compute depth".  N is the record's index
+ * in the file; with a query it counts within the range walk that met it (a walk numbers its records from its own beginning,
+ * and its first record is compared with none).  What has been written by then is unspecified.
+ *
+ * Limits.  A depth is held in 32 bits: more than 2^31 - 1 counted records over one position are outside the contract.
+ */
+#ifndef NGSQ_DEPTH_H
+#define NGSQ_DEPTH_H
+
+#include "ngsq.h"
+#include "ngsq_bam.h"
+#include "ngsq_view.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* the default of --exclude-flags: unmapped, secondary, QC-fail, duplicate (0x4 | 0x100 | 0x200 | 0x400), as `samtools depth` */
+#define NGSQ_DEPTH_EXCLUDE_FLAGS 1796u
+
+/* What one call did. */
+typedef struct ngsq_depth_report {
+    uint64_t records_scanned; /* records the device ingest handed out */
+    uint64_t records_counted; /* records that count (the filters above) and, with a query, belong to the region's walks and
+                                 meet [S-1, min(E, L)); a counted record may still cover nothing (no span, a start at or beyond L) */
+    uint64_t runs;            /* lines written */
+    uint64_t text_bytes;      /* bytes written */
+    uint64_t sequences;       /* sequences (or the one region) with at least one line */
+    uint64_t tiles;           /* tiles of tile_positions the run path took */
+    uint64_t batches;         /* batches of the device ingest */
+    uint64_t ranges;          /* range walks (0 without a query: one walk of the whole file) */
+    double scan_ms;           /* host time inside the device ingest's calls */
+    double add_ms;            /* GPU time of the order check and of the kernel that adds the records to the difference array */
+    double runs_ms;           /* GPU time of the run kernels: sums, run starts, depths */
+    double format_ms;         /* GPU time of the size pass, its scan and the write pass */
+    double copy_ms;           /* GPU time of the device-to-host copies of the text */
+    double write_ms;          /* the writer thread's time inside write(2) */
+    double total_ms;          /* wall clock of the call */
+} ngsq_depth_report;
+
+/* The tile size in force for a request: 0 asks for the default; any request of at least 1 is accepted and rounded up to the
+ * kernels' granule (a block's positions).  Pure; needs no GPU. */
+uint64_t ngsq_depth_tile_positions(uint64_t requested);
+
+/* Write the depth of `bam` (opened by ngsq_bam_open, no batch read yet) to the file descriptor fd, as described above.
+ * query NULL: the whole file, no index needed.  Otherwise the region, through the index bai_path (NULL: "<path of bam>.bai");
+ * the query and the index are looked at before the first byte is written, and their errors are those of ngsq_bam_query_chunks.
+ * exclude_flags <= 65535, min_mapq <= 255.  batch_records: records per ingest batch (0: the default).  coalesce_gap: as in
+ * ngsq_bam_view.  tile_positions: positions of a sequence the run path takes at a time (ngsq_depth_tile_positions).
+ * Errors through ngsq_bam_last_error(): those above; "writing depth to stream: <strerror> (os error N)" for a failing write.
+ * out (optional) receives the report. */
+int ngsq_bam_depth(ngsq_bam *bam, ngsq_ctx *ctx, int fd, const char *query, const char *bai_path, uint32_t exclude_flags,
+                   uint32_t min_mapq, uint64_t batch_records, uint64_t coalesce_gap, uint64_t tile_positions, ngsq_depth_report *out);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

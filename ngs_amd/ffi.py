@@ -289,6 +289,17 @@ class ViewReport(C.Structure):
                 ("write_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+# ---- include/ngsq_depth.h ---------------------------------------------------------------------
+DEPTH_EXCLUDE_FLAGS = 1796
+
+
+class DepthReport(C.Structure):
+    _fields_ = [("records_scanned", C.c_uint64), ("records_counted", C.c_uint64), ("runs", C.c_uint64), ("text_bytes", C.c_uint64),
+                ("sequences", C.c_uint64), ("tiles", C.c_uint64), ("batches", C.c_uint64), ("ranges", C.c_uint64),
+                ("scan_ms", C.c_double), ("add_ms", C.c_double), ("runs_ms", C.c_double), ("format_ms", C.c_double),
+                ("copy_ms", C.c_double), ("write_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 # ---- include/ngsq_generate.h ------------------------------------------------------------------
 GENERATE_MAX_TABLE = 1 << 20
 GENERATE_MAX_ATTEMPTS = 1024
@@ -507,6 +518,10 @@ PROTOTYPES = {
     "ngsq_bam_query_chunks": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, u32p, u64p, u64p, C.POINTER(ViewChunk), C.c_uint64, u64p]),
     "ngsq_bam_view": (C.c_int, [C.c_void_p, ctx_p, C.c_int, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint64, C.c_uint64,
                                 C.POINTER(ViewReport)]),
+    # include/ngsq_depth.h
+    "ngsq_depth_tile_positions": (C.c_uint64, [C.c_uint64]),
+    "ngsq_bam_depth": (C.c_int, [C.c_void_p, ctx_p, C.c_int, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
+                                 C.c_uint64, C.POINTER(DepthReport)]),
     # include/ngsq_generate.h
     "ngsq_generate_last_error": (C.c_char_p, []),
     "ngsq_generate_parse_provider": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(GenerateProvider), C.c_char_p, C.c_size_t]),

@@ -764,6 +764,36 @@ def bam_view(path: str, out_path: str, query: Optional[str] = None, mode: str = 
         return run(bam, ctx)
 
 
+def depth_tile_positions(requested: int = 0, lib=None) -> int:
+    """The tile size `ngs depth` takes a sequence by for a request (include/ngsq_depth.h): 0 asks for the default, anything else
+    is rounded up to the kernels' granule.  Pure, needs no GPU."""
+    lib = lib or ffi.load_library()
+    return int(lib.ngsq_depth_tile_positions(requested))
+
+
+def bam_depth(path: str, out_path: str, query: Optional[str] = None, exclude_flags: int = ffi.DEPTH_EXCLUDE_FLAGS, min_mapq: int = 0,
+              batch_records: int = 0, coalesce_gap: int = 0, tile_positions: int = 0, device: int = 0, bai_path: Optional[str] = None,
+              lib=None) -> Dict[str, float]:
+    """`ngs depth <BAM> [QUERY]` in process (include/ngsq_depth.h): the per-base depth of the coordinate-sorted BAM `path`, or of
+    one region of it, written to out_path (created or truncated) as bedGraph lines, one per run of equal depth.  exclude_flags:
+    records with any of these flag bits do not count; min_mapq: nor do records below it.  batch_records / coalesce_gap /
+    tile_positions: records per ingest batch, the gap below which a query's chunks share a range walk, positions per tile of
+    the run path (0: the library's defaults); the bytes do not depend on them.  bai_path: the index of a query (default
+    "<path>.bai").  Returns the report; NgsqError on an open failure, an unsorted file, a bad query or index, a failed write."""
+    lib = lib or ffi.load_library()
+    q = query.encode() if query is not None else None
+    bai = bai_path.encode() if bai_path else None
+    with _reader_and_plain_context(lib, path, device) as (bam, ctx):
+        fd = os.open(out_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o666)
+        try:
+            rep = ffi.DepthReport()
+            _check_bam(lib.ngsq_bam_depth(bam, ctx, fd, q, bai, exclude_flags, min_mapq, batch_records, coalesce_gap, tile_positions,
+                                          C.byref(rep)), lib)
+            return {k: getattr(rep, k) for k, _ in ffi.DepthReport._fields_}
+        finally:
+            os.close(fd)
+
+
 def _c_strings(items: Sequence[bytes]):
     """(char **, uint32_t *, n) for byte strings that may be empty or hold any byte; keep the result while they are in use."""
     bufs = [C.create_string_buffer(bytes(x), len(x) + 1) for x in items]
