@@ -611,6 +611,10 @@ __device__ __forceinline__ void inflate_block(Lds &L, const uint8_t *__restrict_
             }
             // the stream is at a byte boundary now: copy the source bytes directly, then restart behind them
             const uint32_t byte0 = (uint32_t)(br.consumed_bits() >> 3);
+            if (byte0 + len > in_mis + in_len) { // the copy below reads the block's input directly: a LEN beyond it would read past the buffer
+                err = INF_INPUT_OVERRUN;
+                break;
+            }
             const uint8_t *sp = comp + blk.in_off - in_mis + byte0;
             for (uint32_t done = 0; done < len;) {
                 const uint32_t n = min(len - done, PIECE - (pos - flushed));
