@@ -59,6 +59,8 @@ int ngsq_fasta_index_from_fai(ngsq_fasta *f);
 
 /* Base::try_from(u8): the 4-bit BAM code of a FASTA byte, or -1 (pure; the device kernel uses the same table) */
 int ngsq_fasta_base_code(uint8_t byte);
+/* bytes of a record's text one workgroup converts at a time (256 threads, tile / 256 bytes each): tests place their edges by it */
+uint32_t ngsq_fasta_tile_bytes(void);
 
 /*
  * Load the reference of a context created with ngsq_config.ref_bases_deferred = 1: for every sequence r of the context

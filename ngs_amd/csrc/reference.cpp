@@ -210,6 +210,8 @@ const char *ngsq_fasta_last_error(void) { return g_fa_err.c_str(); }
 
 int ngsq_fasta_base_code(uint8_t byte) { return ngsq::fasta_base_code(byte); }
 
+uint32_t ngsq_fasta_tile_bytes(void) { return ngsq::FASTA_TILE; }
+
 int ngsq_fasta_open(const char *path, int n_threads, ngsq_fasta **out) {
     if (!path || !out) return fa_fail(NGSQ_ERR_INVALID_ARGUMENT, "null argument");
     *out = nullptr;

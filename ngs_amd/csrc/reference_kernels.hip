@@ -18,6 +18,7 @@ namespace {
 
 constexpr uint32_t TILE = FASTA_TILE; // bytes of text per tile
 constexpr uint32_t THREADS = 256;     // 16 bytes per thread
+static_assert(TILE == 16 * THREADS, "load_own gives a thread one uint4: the tile is 16 bytes for each of THREADS threads");
 
 // Base::try_from(u8) (noodles-sam 0.25 record/sequence/base.rs: the char, upper-cased, is one of "=ACMGRSVTWYHKDBN")
 __host__ __device__ inline uint32_t base_code_of(uint32_t c) {

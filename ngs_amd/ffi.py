@@ -462,6 +462,7 @@ PROTOTYPES = {
     "ngsq_fasta_index_seconds": (C.c_double, [C.c_void_p]),
     "ngsq_fasta_index_from_fai": (C.c_int, [C.c_void_p]),
     "ngsq_fasta_base_code": (C.c_int, [C.c_uint8]),
+    "ngsq_fasta_tile_bytes": (C.c_uint32, []),
     "ngsq_reference_load": (C.c_int, [ctx_p, C.c_void_p, C.POINTER(C.c_char_p), u8p]),
     "ngsq_reference_wait": (C.c_int, [ctx_p]),
     "ngsq_reference_get_stats": (C.c_int, [ctx_p, C.POINTER(ReferenceStats)]),

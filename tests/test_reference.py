@@ -5,11 +5,12 @@ that is no base letter fails the reads over it and no others; a FASTA sequence s
 run past its end).
 
 CPU: the definition-line index (scan and .fai), the byte -> code table against the oracle's restatement, the hand golden
-through the oracle.  GPU (-m gpu): file -> pinned -> HIP conversion kernels -> Edits kernels against the oracle fed the same
+through the oracle; every input of tests/test_reference_layout_gpu.py held to the edge it is named for (test_case_*).  GPU (-m gpu): file -> pinned -> HIP conversion kernels -> Edits kernels against the oracle fed the same
 file parsed in Python."""
 import ctypes as C
 import json
 import os
+import re
 
 import numpy as np
 import pytest
@@ -412,3 +413,143 @@ def test_missing_and_unwanted_sequences(gpu_lib, oracle_mod, tmp_path):
     assert gpu_lib.ngsq_reference_load(cfg_ctx._ctx, h, arr, None) == ffi.ERR_STATE
     gpu_lib.ngsq_fasta_close(h)
     cfg_ctx.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the inputs of tests/test_reference_layout_gpu.py (tests/fasta_cases.py), each held to the edge it is named for -- no GPU.  The
+# records' text offsets come from the model (record_spans) and are cross-checked with the library's index.
+# ---------------------------------------------------------------------------------------------------------------------
+from tests import fasta_cases as fc  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def T(lib):
+    t = int(lib.ngsq_fasta_tile_bytes())
+    assert t % 256 == 0 and t // 256 == 16                                # 256 threads of 16 bytes: the phases of case a
+    return t
+
+
+def held_texts(lib, tmp_path, case):
+    """{record: its text} by the model's offsets, which the library's index must share"""
+    p = str(tmp_path / "case.fa")
+    open(p, "wb").write(case.text)
+    spans = fc.record_spans(case.text)
+    n, recs, from_fai = fasta_index(lib, p)
+    assert n == len(spans) and not from_fai
+    assert recs == [(nm, e - b) for nm, b, e in spans]
+    assert len({nm for nm, _, _ in spans}) == len(spans)
+    return {nm: case.text[b:e] for nm, b, e in spans}
+
+
+def test_case_a_terminators_at_every_phase_of_a_threads_bytes(lib, tmp_path, T):
+    case = fc.case_thread_phases(T)
+    texts, seqs = held_texts(lib, tmp_path, case), fc.sequences(case.text)
+    assert len(texts) == 64
+    for tname, term in fc.TERMINATORS.items():
+        for ph in range(16):
+            name = f"{tname}{ph}"
+            t, (held, off) = texts[name], case.holds[name]
+            assert held == term and t[off:off + len(term)] == term and off % 16 == ph and off // 16 == 1
+            assert t.count(b"\r") == term.count(b"\r") and t.count(b"\n") == 2 - (tname == "cr")
+            assert chr(t[off + len(term)]) in "ACGTacgt"                  # a letter behind it
+            kept_cr = {"lf": 0, "crlf": 0, "cr": 1, "crcrlf": 1}[tname]   # the '\r's that stay bytes of the sequence
+            assert len(seqs[name]) == 66 + ph + kept_cr and seqs[name].count(b"\r") == kept_cr and b"\n" not in seqs[name]
+    assert texts["crlf15"][31:33] == b"\r\n"                              # the '\n' is the next thread's first byte
+
+
+@pytest.mark.parametrize("ending", list(fc.LAST_RECORDS))
+@pytest.mark.parametrize("residue", [0, 1])
+def test_case_b_terminators_and_record_ends_on_the_tile(lib, tmp_path, T, ending, residue):
+    case = fc.case_tile_edges(T, ending, residue)
+    texts, seqs = held_texts(lib, tmp_path, case), fc.sequences(case.text)
+    where = {"nl_Tm1": (T - 1, b"\n"), "nl_T": (T, b"\n"), "crnl_Tm1": (T - 1, b"\r\n"), "cr_Tm1": (T - 1, b"\r"), "crcrnl_Tm2": (T - 2, b"\r\r\n")}
+    assert case.holds["bytes"] == where
+    for name, (off, b) in where.items():
+        assert texts[name][off:off + len(b)] == b and texts[name][off - 1:off] not in (b"\r", b"\n")
+        assert texts[name].find(b"\r") in (-1, off) and texts[name].find(b"\n") == off + len(b) - 1 + (b == b"\r") * 51
+    assert seqs["cr_Tm1"][T - 1:T] == b"\r" and seqs["crcrnl_Tm2"][T - 2:T - 1] == b"\r" and seqs["crnl_Tm1"].count(b"\r") == 0
+    assert {nm: len(texts[nm]) for nm in ("len_Tm1", "len_T", "len_Tp1", "len_2T")} == {"len_Tm1": T - 1, "len_T": T, "len_Tp1": T + 1, "len_2T": 2 * T}
+    assert all(texts[nm].endswith(b"\n") for nm in ("len_Tm1", "len_T", "len_Tp1", "len_2T"))
+    last, end = texts["last"], fc.LAST_RECORDS[ending]
+    assert case.text.endswith(b">last\n" + last) and len(last) % 16 == residue and len(last) == case.holds["length"]["last"]
+    assert last.endswith(end) and chr(last[len(last) - len(end) - 1]) in "ACGTacgt"
+    assert len(seqs["last"]) == len(last) - 1 - len(end) and b"\r" not in seqs["last"]   # (the one '\n' inside; the ending is no base)
+
+
+def test_case_c_tiles_of_0_1_2_3_and_5_bases_at_every_alignment(lib, tmp_path, T):
+    case = fc.case_thin_tiles(T)
+    texts, seqs = held_texts(lib, tmp_path, case), fc.sequences(case.text)
+    for v in range(4):
+        per_tile = fc.tile_bases(texts[f"thin{v}"], T)
+        assert per_tile == case.holds[f"thin{v}"] == [v + 1, 0, 1, 0, 2, 0, 3, 0, 5, 0, 60]
+        assert b"\r" not in texts[f"thin{v}"] and len(seqs[f"thin{v}"]) == v + 72
+        gaps = [len(g) for g in re.findall(rb"\n+", texts[f"thin{v}"])]
+        assert gaps[0] >= T + 5 and all(g >= T for g in gaps[:5])
+    for k in (2, 4, 6, 8, 10):                                            # where the tile's codes go: every alignment mod 4
+        assert {sum(case.holds[f"thin{v}"][:k]) % 4 for v in range(4)} == {0, 1, 2, 3}
+    assert texts["blank_crlf"] == b"\r\n" * 40 and seqs["blank_crlf"] == b"" and fc.tile_bases(texts["blank_crlf"], T) == [0]
+
+
+def test_case_d_every_byte_value_at_a_known_position(lib, tmp_path, T, oracle_mod):
+    case = fc.case_every_byte(T)
+    texts, seqs = held_texts(lib, tmp_path, case), fc.sequences(case.text)
+    every = case.holds["all"]
+    assert sorted(every) == [v for v in range(256) if v != 10] and list(every) == sorted(every)
+    assert b"\r\n" not in case.text and case.text.count(b"\n>") == 3     # no '>' in a first column but the four records' own
+    for name, w in case.holds["widths"].items():
+        assert seqs[name] == every                                        # value v at position v (v < 10) or v - 1
+        assert max(len(line) for line in texts[name].split(b"\n")) <= w + 2
+        codes = oracle_mod.fasta_codes(seqs[name])
+        assert int((codes > 15).sum()) == 255 - 32 + 1                    # (32 letters, '=' has no other case)
+        assert np.array_equal(codes, fc.CODE_OF[np.frombuffer(every, dtype=np.uint8)])
+    assert min(len(line) for line in texts["all_w1"].split(b"\n")[:-1]) == 1
+    both = fc.CODE_OF[np.frombuffer(seqs["letters"], dtype=np.uint8)]
+    assert seqs["letters"] == case.holds["letters"] and both.max() == 15 and set(both[:32]) == set(range(16))
+    assert set(seqs["letters"]) == set((LETTERS + LETTERS.lower()).encode())
+
+
+def test_case_e_many_records_with_empty_ones_between(lib, tmp_path, T):
+    case = fc.case_many_records(T)
+    texts, seqs = held_texts(lib, tmp_path, case), fc.sequences(case.text)
+    assert len(texts) == 3000 and len(case.names) == 1500 and sorted(int(n[1:]) for n in case.names) == list(range(1, 3000, 2))
+    assert case.names != sorted(case.names, key=lambda n: int(n[1:]))     # shuffled
+    own = [len(seqs[n]) for n in case.names]
+    assert 0 <= min(map(len, seqs.values())) and max(map(len, seqs.values())) <= 40
+    assert sum(L < o for L, o in zip(case.lens, own)) == 40 and sum(L > o for L, o in zip(case.lens, own)) == 40
+    empty = [len(seqs[f"r{i}"]) == 0 for i in range(3000)]
+    runs = [len(r) for r in "".join("e" if x else "." for x in empty).split(".") if r]
+    assert max(runs) == 5 == case.holds["empty_runs"] and len(runs) > 50
+    assert any(empty[i] for i in range(1, 3000, 2)) and any(empty[i] for i in range(0, 3000, 2))
+    assert {texts[f"r{i}"] for i in range(3000) if empty[i]} == {b"", b"\n", b"\r\n"}
+
+
+@pytest.mark.parametrize("extra", [1, 100])
+def test_case_f_a_record_of_1025_tiles(lib, tmp_path, T, extra):
+    case = fc.case_scan_rounds(T, extra)
+    texts = held_texts(lib, tmp_path, case)
+    long_ = texts["long"]
+    assert list(texts) == ["front", "long", "back"] and len(long_) == 1024 * T + extra == case.holds["text_bytes"]
+    assert -(-len(long_) // T) == fc.SCAN_ROUND + 1
+    assert long_.find(b"\n") == 60 and set(long_) == set(b"ACGTacgt\n")
+    assert [len(s) for s in fc.sequences(case.text).values()] == [700, fc.bases_for_text(len(long_), 60), 700]
+    # what the second round's offset places: nothing for 1024 T + 1 (the byte is the text's last newline), lines of bases for + 100
+    in_last = fc.tile_bases(long_[fc.SCAN_ROUND * T:], T)
+    assert in_last == ([0] if extra == 1 else [98]) and long_[fc.SCAN_ROUND * T:].count(b"\n") == (1 if extra == 1 else 2)
+
+
+def test_case_g_two_pieces_and_two_turns_of_the_grid(lib, tmp_path, T):
+    case = fc.case_two_pieces(T)
+    texts = held_texts(lib, tmp_path, case)
+    long_ = texts["long"]
+    assert list(texts) == ["front", "long", "back"] and len(long_) == (33 << 20) + 17 == case.holds["text_bytes"]
+    assert fc.PIECE < len(long_) <= 2 * fc.PIECE                          # two pieces
+    assert -(-len(long_) // T) > 16 * 256                                 # a block of min(tiles, 16 per CU) takes a second tile
+    assert long_.find(b"\n") == 70 and long_[fc.PIECE - 1:fc.PIECE + 1].isalpha()
+
+
+@pytest.mark.parametrize("over", [0, 1])
+def test_case_h_refused_bytes_at_the_lists_capacity(lib, tmp_path, T, over):
+    case = fc.case_refused_capacity(T, fc.BAD_CAP + over)
+    texts, seqs = held_texts(lib, tmp_path, case), fc.sequences(case.text)
+    assert fc.BAD_CAP == 65536 and seqs["cap"].count(b"*") == fc.BAD_CAP + over == case.holds["refused"]
+    assert len(seqs["cap"]) == 2 * (fc.BAD_CAP + over) and set(seqs["cap"][0::2]) == set(b"ACGT") and len(case.text) < 200_000
