@@ -2,7 +2,7 @@
  * ngsq_bgzf.h -- BGZF written on the GPU: the device DEFLATE encoder, the counterpart of
  * ngsq_bgzf_inflate_device (ngsq_bam.h).  The input is cut into blocks of NGSQ_BGZF_BLOCK_INPUT bytes; each becomes one
  * complete BGZF block (SAM/BAM specification 4.1) with a dynamic-Huffman DEFLATE payload, or a stored one when that is not
- * smaller.  The output bytes depend on the input bytes alone.
+ * smaller.  The output bytes depend on the input bytes and the context's effort (below) alone.
  *
  * Messages: ngsq_last_error(ctx).
  */
@@ -32,6 +32,20 @@ typedef struct ngsq_bgzf_deflate_report {
  * work); without the flag, nothing.  rep may be NULL. */
 int ngsq_bgzf_deflate_device(ngsq_ctx *ctx, const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t out_cap, uint64_t *out_len,
                              uint32_t flags, ngsq_bgzf_deflate_report *rep);
+
+/* The encoder's effort, a property of the context: every encoder launch made for the context reads it -- the call above, the BAM
+ * writers of ngsq_samtext.h and ngsq_bamsort.h, and ngsq_generate_write_bgzf through the context given to ngsq_generate_load.
+ * NORMAL is the encoder of a context that was never told.  HIGH searches harder for matches (candidates inside a position's own
+ * tile, several candidates per position, a lazy parse) and costs encoder time; no block is larger than at NORMAL.  The output
+ * bytes depend on the input bytes and the effort alone. */
+#define NGSQ_BGZF_EFFORT_NORMAL 0u
+#define NGSQ_BGZF_EFFORT_HIGH 1u
+/* NGSQ_ERR_INVALID_ARGUMENT, with a message, for another value or a null context. */
+int ngsq_bgzf_set_effort(ngsq_ctx *ctx, uint32_t effort);
+uint32_t ngsq_bgzf_effort(const ngsq_ctx *ctx); /* (a null context: NORMAL) */
+/* Match candidates a position looks at beside the one at distance 1: 1 at NORMAL, the length of the hash chain walked at HIGH;
+ * 0 for another value.  Host, pure. */
+uint32_t ngsq_bgzf_effort_candidates(uint32_t effort);
 
 #ifdef __cplusplus
 }

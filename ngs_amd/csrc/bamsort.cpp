@@ -113,7 +113,7 @@ int write_sorted(ngsq_bam *b, ngsq_ctx *c, int fd, uint64_t max_records, uint64_
 
     // phase 1: every batch's records copied into a slab, nothing compressed.  (R's failures leave their message in R.err.)
     auto keep_all = [&]() -> int {
-        if (const int rc = R.begin(c->device, st)) return rc;
+        if (const int rc = R.begin(c->device, st, c->bgzf_effort)) return rc;
         for (auto &e : ev.e) BHIP(hipEventCreate(&e));
         BHIP(span.reserve(SP_WORDS * sizeof(unsigned long long)));
         const unsigned long long *const sp = static_cast<const unsigned long long *>(span.h);

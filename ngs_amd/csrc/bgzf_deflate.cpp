@@ -34,6 +34,20 @@ extern "C" {
 
 uint64_t ngsq_bgzf_deflate_bound(uint64_t in_len, uint32_t flags) { return deflate_bound(in_len) + ((flags & NGSQ_BGZF_EOF) ? 28u : 0u); }
 
+int ngsq_bgzf_set_effort(ngsq_ctx *c, uint32_t effort) {
+    static_assert(NGSQ_BGZF_EFFORT_NORMAL == DEFLATE_EFFORT_NORMAL && NGSQ_BGZF_EFFORT_HIGH == DEFLATE_EFFORT_HIGH, "one numbering");
+    if (!c) return zfail(c, NGSQ_ERR_INVALID_ARGUMENT, "null argument");
+    if (effort > NGSQ_BGZF_EFFORT_HIGH) return zfail(c, NGSQ_ERR_INVALID_ARGUMENT, "unknown effort %u (0: normal, 1: high)", effort);
+    c->bgzf_effort = effort;
+    return NGSQ_OK;
+}
+
+uint32_t ngsq_bgzf_effort(const ngsq_ctx *c) { return c ? c->bgzf_effort : NGSQ_BGZF_EFFORT_NORMAL; }
+
+uint32_t ngsq_bgzf_effort_candidates(uint32_t effort) {
+    return effort == NGSQ_BGZF_EFFORT_NORMAL ? 1u : effort == NGSQ_BGZF_EFFORT_HIGH ? DEFLATE_CHAIN_K : 0u;
+}
+
 int ngsq_bgzf_deflate_device(ngsq_ctx *c, const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t out_cap, uint64_t *out_len, uint32_t flags,
                              ngsq_bgzf_deflate_report *rep) {
     if (rep) memset(rep, 0, sizeof *rep);
@@ -65,7 +79,7 @@ int ngsq_bgzf_deflate_device(ngsq_ctx *c, const uint8_t *in, uint64_t in_len, ui
         ZHIP(hipEventRecord(ev.e[4], st));
         ZHIP(hipMemcpyAsync(d_in.p, in, in_len, hipMemcpyHostToDevice, st));
         ZHIP(hipMemsetAsync(d_in.p + in_len, 0, DEFLATE_IN_SLACK, st));
-        ZHIP(launch_bgzf_deflate(d_in.p, in_len, d_out.p, sc, static_cast<unsigned long long *>(hw.dev), st, ev.e));
+        ZHIP(launch_bgzf_deflate(d_in.p, in_len, d_out.p, sc, static_cast<unsigned long long *>(hw.dev), c->bgzf_effort, st, ev.e));
         ZHIP(hipStreamSynchronize(st));
         const unsigned long long *const h = static_cast<const unsigned long long *>(hw.h);
         bytes = h[DH_BYTES];

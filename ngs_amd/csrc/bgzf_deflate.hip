@@ -17,6 +17,10 @@
 // k_deflate_crc computes the blocks' CRC32 (bgzf_crc.h), the ingest's scan turns the member sizes into offsets, and k_deflate_pack
 // writes header, payload and trailer contiguously.  Nothing depends on the grid or on the order of arrival: the same input gives
 // the same bytes.
+// High effort (k_bgzf_deflate<true>) changes (1) and (2): the table is updated wave by wave, so that a position
+// sees its own tile; what a position reads there links it to the previous position of its hash, and several candidates are
+// walked along the links; the parse looks one position ahead before it takes a short match.  The block is sized both ways and the
+// smaller parse is emitted.  Normal effort (k_bgzf_deflate<false>) is the encoder as it was, to the byte.
 #include <hip/hip_runtime.h>
 
 #include "bgzf_crc.h"
@@ -31,6 +35,9 @@ constexpr uint32_t DEF_WAVES = DEF_THREADS / 64;
 constexpr uint32_t HASH_BITS = 14;
 constexpr uint32_t PARSE_TILE = 4096;
 constexpr uint32_t MIN_MATCH = 4, MAX_MATCH = 258, MAX_DIST = 32768;
+// high effort: a match of LAZY_BELOW bytes or more is taken at once, a shorter one waits for the look at the
+// next position (zlib's max_lazy).  (The candidates a position walks along its hash chain: DEFLATE_CHAIN_K, deflate_kernels.h.)
+constexpr uint32_t LAZY_BELOW = 32;
 // alphabets inside the unified symbol arrays: literal/length at 0 (286), distance at 288 (30), code lengths at 320 (19)
 constexpr uint32_t A_LL = 0, A_D = 288, A_CL = 320, A_END = 340;
 constexpr uint32_t N_LL = 286, N_D = 30, N_CL = 19;
@@ -231,10 +238,14 @@ __device__ __forceinline__ void assign_code(DLds &L, uint32_t a, uint32_t base, 
     L.code[base + i] = (uint16_t)(__builtin_bitreverse32(c) >> (32u - l));
 }
 
-// One block: in[0, n) -> its DEFLATE payload at `stage` (dynamic) or nothing (stored); the payload's bytes and the flag.
-__device__ void deflate_block(DLds &L, const uint8_t *__restrict__ in, uint32_t n, uint16_t *__restrict__ dist,
-                              unsigned long long *__restrict__ stage, uint64_t *__restrict__ size_out, uint32_t *__restrict__ flag_out,
-                              unsigned long long *__restrict__ work) {
+// Steps (0) to (4) of one block: the tokens of in[0, n) (L.mask, L.len8, dist), their codes, and the bits of the dynamic block,
+// which is the value.  HIGH searches harder in (1) and (2): the table is updated wave by wave, so that a position sees the
+// positions of its own tile; the value a position reads there is its link to the previous position of the same hash (`link`,
+// position + 1, 0: none), and DEFLATE_CHAIN_K candidates are walked along the links; the parse looks one position ahead.  Everything
+// the steps read of L they have written: a block may be taken through them more than once.
+template <bool HIGH>
+__device__ __forceinline__ uint32_t deflate_tokens(DLds &L, const uint8_t *__restrict__ in, uint32_t n, uint16_t *__restrict__ dist,
+                                                   uint16_t *link) {
     const uint32_t tid = threadIdx.x;
     // ---- (0) clear; the byte histogram and the literal cost
     for (uint32_t k = tid; k < (1u << HASH_BITS); k += DEF_THREADS) L.u.hash[k] = 0;
@@ -274,10 +285,23 @@ __device__ void deflate_block(DLds &L, const uint8_t *__restrict__ in, uint32_t 
         if (act) {
             w = ld32u(in + p);
             h = (w * 2654435761u) >> (32u - HASH_BITS);
-            cand = L.u.hash[h];
+            if (!HIGH) cand = L.u.hash[h];
         }
-        __syncthreads();
-        if (act) atomicMax(&L.u.hash[h], p + 1u);
+        if (HIGH) {
+            // the waves take turns: all lanes of a wave read, then all update, so the table after a turn depends on the
+            // positions alone, and a wave sees every position of the waves before it
+            for (uint32_t turn = 0; turn < DEF_WAVES; turn++) {
+                if ((tid >> 6) == turn && act) {
+                    cand = L.u.hash[h];
+                    link[p] = (uint16_t)cand;
+                    atomicMax(&L.u.hash[h], p + 1u);
+                }
+                __syncthreads();
+            }
+        } else {
+            __syncthreads();
+            if (act) atomicMax(&L.u.hash[h], p + 1u);
+        }
         uint32_t best_len = 0, best_d = 1;
         if (act) {
             const uint32_t maxlen = n - p < MAX_MATCH ? n - p : MAX_MATCH;
@@ -287,13 +311,30 @@ __device__ void deflate_block(DLds &L, const uint8_t *__restrict__ in, uint32_t 
                 const int gain = (int)(l * hq) - 12 * 16;
                 if (l >= MIN_MATCH && gain > 0) best_len = l, best_d = 1, best_gain = gain;
             }
-            if (cand) {
+            if (!HIGH && cand) {
                 const uint32_t c = cand - 1u, d = p - c; // (c is of an earlier tile: c < t0 <= p)
                 if (d >= 2u && d <= MAX_DIST && ld32u(in + c) == w) {
                     const uint32_t l = match_len(in + p, in + c, maxlen);
                     const uint32_t de = d <= 4u ? 0u : ilog2(d - 1u) - 1u;
                     const int gain = (int)(l * hq) - (int)(12u + de) * 16;
                     if (l >= MIN_MATCH && gain > best_gain) best_len = l, best_d = d, best_gain = gain;
+                }
+            }
+            if (HIGH) {
+                // Along the links, nearest first (c is of an earlier wave's turn: c < p; links only go further back).  A distance
+                // costs no less than a nearer one, so only a longer match can gain more than the best so far: a candidate
+                // that differs at the byte behind the best length is not extended, and nothing is longer than maxlen.
+                uint32_t next = cand;
+                for (uint32_t k = 0; k < DEFLATE_CHAIN_K && next && best_len < maxlen; k++) {
+                    const uint32_t c = next - 1u, d = p - c;
+                    if (d > MAX_DIST) break;
+                    if (d >= 2u && ld32u(in + c) == w && in[c + best_len] == in[p + best_len]) {
+                        const uint32_t l = match_len(in + p, in + c, maxlen);
+                        const uint32_t de = d <= 4u ? 0u : ilog2(d - 1u) - 1u;
+                        const int gain = (int)(l * hq) - (int)(12u + de) * 16;
+                        if (l >= MIN_MATCH && gain > best_gain) best_len = l, best_d = d, best_gain = gain;
+                    }
+                    next = link[c];
                 }
             }
         }
@@ -304,7 +345,7 @@ __device__ void deflate_block(DLds &L, const uint8_t *__restrict__ in, uint32_t 
         __syncthreads();
     }
 
-    // ---- (2) the greedy parse: one lane per 4 KiB tile
+    // ---- (2) the parse, greedy (at high effort with the lazy step): one lane per 4 KiB tile
     const uint32_t n_tiles = (n + PARSE_TILE - 1u) / PARSE_TILE;
     if (tid < n_tiles) {
         uint32_t p = tid * PARSE_TILE;
@@ -323,6 +364,17 @@ __device__ void deflate_block(DLds &L, const uint8_t *__restrict__ in, uint32_t 
             if (len > end - p) { // cut at the tile's edge; a rest below the minimum is a literal
                 len = end - p >= MIN_MATCH ? end - p : 0u;
                 L.len8[p] = (uint8_t)(len ? len - 3u : 0u);
+            }
+            if (HIGH && len && len < LAZY_BELOW && p + 1u < end) {
+                // The lazy step: a longer match at p + 1 makes p a literal.  Both lengths are the cut ones, and p + 1 is of this
+                // lane's tile: a match the edge has cut reaches the edge, and none at p + 1 reaches further.
+                const uint32_t v1 = L.len8[p + 1u];
+                uint32_t l1 = v1 ? v1 + 3u : 0u;
+                l1 = l1 < end - p - 1u ? l1 : end - p - 1u;
+                if (l1 > len) {
+                    len = 0;
+                    L.len8[p] = 0;
+                }
             }
             p += len ? len : 1u;
         }
@@ -391,7 +443,29 @@ __device__ void deflate_block(DLds &L, const uint8_t *__restrict__ in, uint32_t 
         if (mat) atomicAdd(&L.matches, mat);
     }
     __syncthreads();
-    const uint32_t total_bits = HDR_FIXED_BITS + L.total_bits;
+    return HDR_FIXED_BITS + L.total_bits;
+}
+
+// One block: in[0, n) -> its DEFLATE payload at `stage` (dynamic) or nothing (stored); the payload's bytes and the flag.  At high
+// effort the block is sized both ways before a bit is written, and the smaller parse is the one emitted (the high one when they
+// are equal): a block is never larger than at normal effort.
+template <bool HIGH>
+__device__ void deflate_block(DLds &L, const uint8_t *__restrict__ in, uint32_t n, uint16_t *__restrict__ dist, uint16_t *link,
+                              unsigned long long *__restrict__ stage, uint64_t *__restrict__ size_out, uint32_t *__restrict__ flag_out,
+                              unsigned long long *__restrict__ work) {
+    const uint32_t tid = threadIdx.x;
+    uint32_t total_bits;
+    if (HIGH) {
+        const uint32_t normal_bits = deflate_tokens<false>(L, in, n, dist, link);
+        __syncthreads(); // (the sum has been read before the next pass clears it)
+        total_bits = deflate_tokens<true>(L, in, n, dist, link);
+        if (normal_bits < total_bits) { // (uniform)
+            __syncthreads();
+            total_bits = deflate_tokens<false>(L, in, n, dist, link);
+        }
+    } else {
+        total_bits = deflate_tokens<false>(L, in, n, dist, link);
+    }
     const uint32_t dyn_bytes = (total_bits + 7u) / 8u, stored_bytes = n + DEFLATE_STORED_EXTRA;
     const bool stored = dyn_bytes >= stored_bytes;
     if (tid == 0) {
@@ -463,12 +537,14 @@ __device__ void deflate_block(DLds &L, const uint8_t *__restrict__ in, uint32_t 
     for (uint32_t k = tid; k < words; k += DEF_THREADS) stage[k] = L.u.stage[k];
 }
 
+template <bool HIGH>
 __global__ __launch_bounds__(DEF_THREADS) void k_bgzf_deflate(const uint8_t *__restrict__ in, uint64_t n, uint32_t n_blocks,
-                                                              uint16_t *__restrict__ dist, uint8_t *__restrict__ stage,
+                                                              uint16_t *__restrict__ dist, uint16_t *link, uint8_t *__restrict__ stage,
                                                               uint64_t *__restrict__ size, uint32_t *__restrict__ flags,
                                                               unsigned long long *__restrict__ work) {
     __shared__ DLds L;
     uint16_t *const my_dist = dist + (size_t)blockIdx.x * 65536u;
+    uint16_t *const my_link = HIGH ? link + (size_t)blockIdx.x * 65536u : nullptr;
     for (;;) {
         if (threadIdx.x == 0) L.ticket = (uint32_t)atomicAdd(&work[0], 1ull);
         __syncthreads();
@@ -476,7 +552,7 @@ __global__ __launch_bounds__(DEF_THREADS) void k_bgzf_deflate(const uint8_t *__r
         if (bi >= n_blocks) return;
         const uint64_t at = (uint64_t)bi * DEFLATE_BLOCK_INPUT;
         const uint32_t len = (uint32_t)(n - at < DEFLATE_BLOCK_INPUT ? n - at : DEFLATE_BLOCK_INPUT);
-        deflate_block(L, in + at, len, my_dist, reinterpret_cast<unsigned long long *>(stage + (size_t)bi * DEFLATE_STAGE_STRIDE), size + bi,
+        deflate_block<HIGH>(L, in + at, len, my_dist, my_link, reinterpret_cast<unsigned long long *>(stage + (size_t)bi * DEFLATE_STAGE_STRIDE), size + bi,
                       flags + bi, work);
         __syncthreads(); // the next block's first LDS writes (the ticket among them) come after this block's last reads
     }
@@ -552,9 +628,10 @@ __global__ __launch_bounds__(PACK_THREADS) void k_deflate_pack(const uint8_t *__
 
 } // namespace
 
-hipError_t launch_bgzf_deflate(const uint8_t *in, uint64_t n, uint8_t *out, DeflateScratch &sc, unsigned long long *host, hipStream_t s,
-                               hipEvent_t *ev) {
+hipError_t launch_bgzf_deflate(const uint8_t *in, uint64_t n, uint8_t *out, DeflateScratch &sc, unsigned long long *host, uint32_t effort,
+                               hipStream_t s, hipEvent_t *ev) {
     const uint64_t nb64 = deflate_blocks(n);
+    if (effort > DEFLATE_EFFORT_HIGH) return hipErrorInvalidValue;
     if (!n || nb64 > 0x7FFFFFFFull) return hipErrorInvalidValue; // (no input: no block, and nothing that would write the host's words)
     const uint32_t n_blocks = (uint32_t)nb64;
     hipError_t e;
@@ -582,7 +659,14 @@ hipError_t launch_bgzf_deflate(const uint8_t *in, uint64_t n, uint8_t *out, Defl
         DTRY(sc.dist.reserve((size_t)grid * 65536u));
         DTRY(sc.crc.reserve(n_blocks));
         DTRY(sc.flags.reserve(n_blocks));
-        hipLaunchKernelGGL(k_bgzf_deflate, dim3(grid), dim3(DEF_THREADS), 0, s, in, n, n_blocks, sc.dist.p, sc.stage.p, sc.off.p, sc.flags.p, sc.work.p);
+        if (effort == DEFLATE_EFFORT_HIGH) {
+            DTRY(sc.link.reserve((size_t)grid * 65536u));
+            hipLaunchKernelGGL(k_bgzf_deflate<true>, dim3(grid), dim3(DEF_THREADS), 0, s, in, n, n_blocks, sc.dist.p, sc.link.p, sc.stage.p, sc.off.p,
+                               sc.flags.p, sc.work.p);
+        } else {
+            hipLaunchKernelGGL(k_bgzf_deflate<false>, dim3(grid), dim3(DEF_THREADS), 0, s, in, n, n_blocks, sc.dist.p, (uint16_t *)nullptr, sc.stage.p,
+                               sc.off.p, sc.flags.p, sc.work.p);
+        }
         DTRY(hipGetLastError());
     }
     DTRY(hipMemsetAsync(sc.off.p + n_blocks, 0, sizeof(uint64_t), s));

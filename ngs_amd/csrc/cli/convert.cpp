@@ -13,6 +13,7 @@
 #include <cerrno>
 
 #include "../../../include/ngsq_bamsort.h"
+#include "../../../include/ngsq_bgzf.h"
 #include "../../../include/ngsq_sam.h"
 #include "../../../include/ngsq_samtext.h"
 #include "cli.h"
@@ -27,6 +28,8 @@ struct ConvertArgs {
     bool write_index = false;              // --write-index: ... and <TO>.bai written beside the sorted BAM
     bool has_sort_memory = false;          // --sort-memory: what the resident records may take of device memory
     unsigned long long sort_memory = 0;
+    bool has_effort = false;               // --gzip-effort: how hard the GPU's encoder searches
+    uint32_t effort = NGSQ_BGZF_EFFORT_NORMAL;
     unsigned long long n = 0;
     int device = 0;
 };
@@ -55,6 +58,9 @@ bool parse_args(int argc, char **argv, int at, ConvertArgs *a) {
                     "      --gzip <WHERE>\n"
                     "          Where BGZF output is compressed (additive, this build): `device` converts SAM to BAM on the GPU;\n"
                     "          `host` changes nothing [default: host] [possible values: host, device]\n"
+                    "      --gzip-effort <EFFORT>\n"
+                    "          With --gzip device (additive, this build): `high` has the GPU's encoder search harder for matches, which\n"
+                    "          gives a smaller BAM for more encoder time [default: normal] [possible values: normal, high]\n"
                     "      --sort <ORDER>\n"
                     "          Order of the records of a BAM written with --gzip device (additive, this build): `coordinate` sorts them\n"
                     "          on the GPU, unplaced records last, and writes SO:coordinate; with it BAM to BAM is converted too, a BAM in\n"
@@ -68,7 +74,8 @@ bool parse_args(int argc, char **argv, int at, ConvertArgs *a) {
                     "          keeps one range of the sorted order [default: the free memory of the device, less 4 GiB]\n\n"
                     "This build converts BAM to SAM, and with --gzip device SAM to BAM: the text is parsed and the BGZF blocks are\n"
                     "written on the GPU, whose encoder has one setting (-c is checked and takes no part).  With --gzip device and\n"
-                    "--sort coordinate it also converts BAM to BAM: the file is inflated, sorted and compressed on the GPU.\n");
+                    "--sort coordinate it also converts BAM to BAM: the file is inflated, sorted and compressed on the GPU.\n"
+                    "One setting as far as -c goes: how hard the encoder searches is chosen with --gzip-effort.\n");
             return false;
         } else if (s == "-n" || s == "--num-records") {
             const std::string v = val("--num-records <USIZE>");
@@ -92,6 +99,12 @@ bool parse_args(int argc, char **argv, int at, ConvertArgs *a) {
             if (v == "host") a->gzip_device = false;
             else if (v == "device") a->gzip_device = true;
             else bail("invalid value '" + v + "' for '--gzip <WHERE>' [possible values: host, device]");
+        } else if (s == "--gzip-effort") {
+            const std::string v = val("--gzip-effort <EFFORT>");
+            if (v == "normal") a->effort = NGSQ_BGZF_EFFORT_NORMAL;
+            else if (v == "high") a->effort = NGSQ_BGZF_EFFORT_HIGH;
+            else bail("invalid value '" + v + "' for '--gzip-effort <EFFORT>' [possible values: normal, high]");
+            a->has_effort = true;
         } else if (s == "--sort") {
             const std::string v = val("--sort <ORDER>");
             if (v == "none") a->sort_coordinate = false;
@@ -132,6 +145,8 @@ std::string existing_index_refusal(const std::string &bai) {
     return "refusing to overwrite existing index file: " + bai + ". Please delete and rerun if you'd like to replace it.";
 }
 
+const char *effort_name(const ConvertArgs &a) { return a.effort == NGSQ_BGZF_EFFORT_HIGH ? "high" : "normal"; }
+
 void log_index_report(const ngsq_index_report &irep) {
     if (g_level >= 3)
         fprintf(stderr, "[ngs] convert: index of %llu records (%llu without coordinates), %llu chunks in %llu bins; device %.1f ms, write %.1f ms\n",
@@ -158,6 +173,12 @@ int sam_to_bam(const ConvertArgs &a, const std::string &from, const std::string 
         close(fd);
         bail(ngsq_last_global_error());
     }
+    if (ngsq_bgzf_set_effort(ctx, a.effort) != NGSQ_OK) {
+        const std::string m = ngsq_last_error(ctx);
+        ngsq_destroy(ctx);
+        close(fd);
+        bail(m);
+    }
     const uint64_t max_records = a.has_n ? std::max<unsigned long long>(a.n, 1) : 0;
     ngsq_samtext_report rep{};
     ngsq_samsort_report srep{};
@@ -175,18 +196,18 @@ int sam_to_bam(const ConvertArgs &a, const std::string &from, const std::string 
     for (uint64_t m = 1; m <= written / 1000000; m++) logf(2, "  [*] Processed %s records.", with_commas(m * 1000000).c_str());
     if (g_level >= 3 && a.sort_coordinate)
         fprintf(stderr, "[ngs] convert: %llu records in %llu chunks sorted in %u of 8 passes, %llu header + %llu text bytes -> %llu BAM bytes in %llu pieces, "
-                        "%llu blocks (%llu stored), %llu compressed; read %.1f ms, up %.1f ms, parse %.1f ms, sort %.1f ms, gather %.1f ms, deflate %.1f ms, "
-                        "down %.1f ms, write %.1f ms, total %.1f ms\n",
+                        "%llu blocks (%llu stored), %llu compressed at effort %s; read %.1f ms, up %.1f ms, parse %.1f ms, sort %.1f ms, gather %.1f ms, "
+                        "deflate %.1f ms, down %.1f ms, write %.1f ms, total %.1f ms\n",
                 (unsigned long long)srep.records, (unsigned long long)srep.chunks, srep.passes_run, (unsigned long long)srep.header_bytes,
                 (unsigned long long)srep.text_bytes, (unsigned long long)srep.bam_bytes, (unsigned long long)srep.pieces, (unsigned long long)srep.blocks,
-                (unsigned long long)srep.stored_blocks, (unsigned long long)srep.compressed_bytes, srep.read_ms, srep.h2d_ms, srep.parse_ms, srep.sort_ms,
+                (unsigned long long)srep.stored_blocks, (unsigned long long)srep.compressed_bytes, effort_name(a), srep.read_ms, srep.h2d_ms, srep.parse_ms, srep.sort_ms,
                 srep.gather_ms, srep.deflate_ms, srep.d2h_ms, srep.write_ms, srep.total_ms);
     else if (g_level >= 3)
         fprintf(stderr, "[ngs] convert: %llu records in %llu chunks, %llu header + %llu text bytes -> %llu BAM bytes in %llu blocks (%llu stored), "
-                        "%llu compressed; read %.1f ms, up %.1f ms, parse %.1f ms, deflate %.1f ms, down %.1f ms, write %.1f ms, total %.1f ms\n",
+                        "%llu compressed at effort %s; read %.1f ms, up %.1f ms, parse %.1f ms, deflate %.1f ms, down %.1f ms, write %.1f ms, total %.1f ms\n",
                 (unsigned long long)rep.records, (unsigned long long)rep.chunks, (unsigned long long)rep.header_bytes,
                 (unsigned long long)rep.text_bytes, (unsigned long long)rep.bam_bytes, (unsigned long long)rep.blocks,
-                (unsigned long long)rep.stored_blocks, (unsigned long long)rep.compressed_bytes, rep.read_ms, rep.h2d_ms, rep.parse_ms,
+                (unsigned long long)rep.stored_blocks, (unsigned long long)rep.compressed_bytes, effort_name(a), rep.read_ms, rep.h2d_ms, rep.parse_ms,
                 rep.deflate_ms, rep.d2h_ms, rep.write_ms, rep.total_ms);
     if (a.write_index) log_index_report(irep);
     return 0;
@@ -217,6 +238,13 @@ int bam_to_sorted_bam(const ConvertArgs &a, const std::string &from, const std::
         close(fd);
         bail(ngsq_last_global_error());
     }
+    if (ngsq_bgzf_set_effort(ctx, a.effort) != NGSQ_OK) {
+        const std::string m = ngsq_last_error(ctx);
+        ngsq_destroy(ctx);
+        ngsq_bam_close(bam);
+        close(fd);
+        bail(m);
+    }
     const uint64_t max_records = a.has_n ? std::max<unsigned long long>(a.n, 1) : 0;
     ngsq_bamsort_report rep{};
     ngsq_index_report irep{};
@@ -231,11 +259,11 @@ int bam_to_sorted_bam(const ConvertArgs &a, const std::string &from, const std::
     for (uint64_t m = 1; m <= rep.records / 1000000; m++) logf(2, "  [*] Processed %s records.", with_commas(m * 1000000).c_str());
     if (g_level >= 3)
         fprintf(stderr, "[ngs] convert: %llu records in %llu batches and %llu slabs sorted in %u of 8 passes, %llu header bytes -> %llu BAM bytes in "
-                        "%llu pieces, %llu blocks (%llu stored), %llu compressed; ingest %.1f ms, keep %.1f ms, sort %.1f ms, gather %.1f ms, "
+                        "%llu pieces, %llu blocks (%llu stored), %llu compressed at effort %s; ingest %.1f ms, keep %.1f ms, sort %.1f ms, gather %.1f ms, "
                         "deflate %.1f ms, down %.1f ms, write %.1f ms, total %.1f ms\n",
                 (unsigned long long)rep.records, (unsigned long long)rep.batches, (unsigned long long)rep.slabs, rep.passes_run,
                 (unsigned long long)rep.header_bytes, (unsigned long long)rep.bam_bytes, (unsigned long long)rep.pieces, (unsigned long long)rep.blocks,
-                (unsigned long long)rep.stored_blocks, (unsigned long long)rep.compressed_bytes, rep.scan_ms, rep.keep_ms, rep.sort_ms, rep.gather_ms,
+                (unsigned long long)rep.stored_blocks, (unsigned long long)rep.compressed_bytes, effort_name(a), rep.scan_ms, rep.keep_ms, rep.sort_ms, rep.gather_ms,
                 rep.deflate_ms, rep.d2h_ms, rep.write_ms, rep.total_ms);
     if (g_level >= 3 && rrep.rounds > 1)
         fprintf(stderr, "[ngs] convert: %llu rounds over %llu walks of the input, budget %llu bytes, survey %llu bytes in %.1f ms\n",
@@ -271,6 +299,8 @@ int convert_main(int argc, char **argv, int at) {
         bail("--write-index needs --gzip device and --sort coordinate and a BAM to write");
     if (a.has_sort_memory && !(a.gzip_device && a.sort_coordinate && tf == "BAM" && (ff == "SAM" || ff == "BAM")))
         bail("--sort-memory needs --gzip device and --sort coordinate and a BAM to write");
+    // (additive) the effort is the device encoder's: refused where no path that runs it is reached
+    if (a.has_effort && !(a.gzip_device && tf == "BAM" && (ff == "SAM" || (ff == "BAM" && a.sort_coordinate)))) bail("--gzip-effort needs --gzip device");
     if (ff == "SAM" && tf == "BAM" && a.gzip_device) return sam_to_bam(a, from, to);
     if (ff == "BAM" && tf == "BAM" && a.gzip_device && a.sort_coordinate) return bam_to_sorted_bam(a, from, to);
     if (reference_only)

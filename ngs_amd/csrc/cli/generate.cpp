@@ -6,6 +6,7 @@
 #include <cmath>
 #include <memory>
 
+#include "../../../include/ngsq_bgzf.h"
 #include "../../../include/ngsq_generate.h"
 #include "cli.h"
 
@@ -17,6 +18,8 @@ struct GenerateArgs {
     unsigned long long n = 0, coverage = 0, seed = 0, batch_pairs = 0;
     int device = 0;
     bool gzip_device = false; // --gzip device: .gz outputs are BGZF written on the GPU
+    bool has_effort = false;  // --gzip-effort: how hard the GPU's encoder searches
+    uint32_t effort = NGSQ_BGZF_EFFORT_NORMAL;
 };
 
 const char *const USAGE = "Usage: ngs generate [OPTIONS] <--num-records <USIZE>|--coverage <USIZE>> <READ_ONES_FILE> <READ_TWOS_FILE> <REFERENCE_PROVIDERS>...";
@@ -71,7 +74,10 @@ bool parse_args(int argc, char **argv, int at, GenerateArgs *a) {
                     "      --gzip <WHERE>\n"
                     "          Where gzipped outputs are compressed (additive, this build): host threads behind a pipe, or the GPU,\n"
                     "          which writes BGZF and sends only compressed bytes to the host; plain outputs are not affected\n"
-                    "          [default: host] [possible values: host, device]\n\n"
+                    "          [default: host] [possible values: host, device]\n"
+                    "      --gzip-effort <EFFORT>\n"
+                    "          With --gzip device (additive, this build): `high` has the GPU's encoder search harder for matches, which\n"
+                    "          gives smaller files for more encoder time [default: normal] [possible values: normal, high]\n\n"
                     "Outputs are FASTQ (.fastq, .fq) or gzipped FASTQ (.fastq.gz, .fq.gz).\n",
                     USAGE);
             return false;
@@ -93,6 +99,12 @@ bool parse_args(int argc, char **argv, int at, GenerateArgs *a) {
             if (v == "host") a->gzip_device = false;
             else if (v == "device") a->gzip_device = true;
             else bail("invalid value '" + v + "' for '--gzip <WHERE>' [possible values: host, device]");
+        } else if (s == "--gzip-effort") {
+            const std::string v = val("--gzip-effort <EFFORT>");
+            if (v == "normal") a->effort = NGSQ_BGZF_EFFORT_NORMAL;
+            else if (v == "high") a->effort = NGSQ_BGZF_EFFORT_HIGH;
+            else bail("invalid value '" + v + "' for '--gzip-effort <EFFORT>' [possible values: normal, high]");
+            a->has_effort = true;
         } else if (s == "--device") {
             a->device = atoi(val("--device <N>").c_str());
         } else if (!s.empty() && s[0] == '-' && s != "-") bail("unexpected argument '" + s + "' found");
@@ -140,6 +152,9 @@ int generate_main(int argc, char **argv, int at) {
         if (a.pos.size() < 3) missing += " <REFERENCE_PROVIDERS>...";
         if (!missing.empty()) bail("the following required arguments were not provided:" + missing);
     }
+    // (additive) the effort is the device encoder's; refused before any file is opened
+    if (a.has_effort && !(a.gzip_device && (detect_format(a.pos[0]) == "Gzipped FASTQ" || detect_format(a.pos[1]) == "Gzipped FASTQ")))
+        bail("--gzip-effort needs --gzip device");
     // (0) the providers: the strings, the FASTA formats, then the files themselves -- before anything is created
     const size_t np = a.pos.size() - 2;
     std::vector<ngsq_generate_provider> prov(np);
@@ -188,6 +203,7 @@ int generate_main(int argc, char **argv, int at) {
         cfg.facets = 0;
         cfg.device = a.device;
         if (ngsq_create(&cfg, &ctx) != NGSQ_OK) msg = ngsq_last_global_error();
+        else if (ngsq_bgzf_set_effort(ctx, a.effort) != NGSQ_OK) msg = ngsq_last_error(ctx);
         else if (ngsq_generate_load(g, ctx) != NGSQ_OK) msg = ngsq_generate_last_error();
     }
     for (int k = 0; k < 2 && msg.empty() && !on_device; k++)
@@ -219,8 +235,8 @@ int generate_main(int argc, char **argv, int at) {
                 (unsigned long long)rep.rejected_start, (unsigned long long)rep.rejected_end, (unsigned long long)rep.rejected_base, rep.draw_ms,
                 rep.format_ms, rep.copy_ms, rep.write_ms, rep.total_ms);
     if (g_level >= 3 && on_device)
-        fprintf(stderr, "[ngs] generate: BGZF on the device: %llu and %llu compressed bytes in %llu blocks (%llu stored), deflate %.1f ms\n",
-                (unsigned long long)zrep.compressed_bytes_one, (unsigned long long)zrep.compressed_bytes_two, (unsigned long long)zrep.blocks,
-                (unsigned long long)zrep.stored_blocks, zrep.deflate_ms);
+        fprintf(stderr, "[ngs] generate: BGZF on the device at effort %s: %llu and %llu compressed bytes in %llu blocks (%llu stored), deflate %.1f ms\n",
+                a.effort == NGSQ_BGZF_EFFORT_HIGH ? "high" : "normal", (unsigned long long)zrep.compressed_bytes_one,
+                (unsigned long long)zrep.compressed_bytes_two, (unsigned long long)zrep.blocks, (unsigned long long)zrep.stored_blocks, zrep.deflate_ms);
     return 0;
 }

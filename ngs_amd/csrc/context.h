@@ -122,6 +122,7 @@ struct ngsq_ctx {
         uint64_t n;
     };
     std::vector<DeferredFeatures> ft_deferred;
+    uint32_t bgzf_effort = 0; // ngsq_bgzf_set_effort: what every encoder launch made for this context runs at
     ngsq::Staging stage[2];
     int stage_next = 0;
     ngsq_kernel_time timing[ngsq::K_COUNT]{};

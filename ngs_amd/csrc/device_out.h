@@ -257,12 +257,13 @@ struct BgzfEncoder {
     unsigned long long *hdev = nullptr;    // (the same words as the device addresses them)
     DevArray<uint8_t> d_comp[2];
     uint64_t comp_bytes = 0, blocks = 0, stored = 0;
+    uint32_t effort = DEFLATE_EFFORT_NORMAL; // the context's (ngsq_bgzf_set_effort), set by whoever starts the encoder
 
     // src[0, bytes) (device, DEFLATE_IN_SLACK readable bytes behind it) into the buffer of `slot`
     hipError_t launch(uint32_t slot, const void *src, uint64_t bytes, hipStream_t st) {
         const hipError_t e = d_comp[slot].reserve(deflate_bound(bytes));
         if (e != hipSuccess) return e;
-        return launch_bgzf_deflate(static_cast<const uint8_t *>(src), bytes, d_comp[slot].p, sc, hdev, st);
+        return launch_bgzf_deflate(static_cast<const uint8_t *>(src), bytes, d_comp[slot].p, sc, hdev, effort, st);
     }
     // The blocks of the launch the caller has waited for: where they lie and how many bytes they are.  nullptr, or what is
     // wrong with them.
@@ -305,8 +306,9 @@ struct BgzfSink {
         hipError_t e_ = (expr);                                                                                 \
         if (e_ != hipSuccess) return fail(NGSQ_ERR_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
     } while (0)
-    // the words, the events, and the writer of fd on `device` (made current)
-    int start(int fd, int device) {
+    // the words, the events, and the writer of fd on `device` (made current); effort: the context's, for every launch
+    int start(int fd, int device, uint32_t effort) {
+        enc.effort = effort;
         ZHIP(hipSetDevice(device));
         ZHIP(hw.reserve(DEFLATE_HOST_WORDS * sizeof(unsigned long long)));
         memset(hw.h, 0, DEFLATE_HOST_WORDS * sizeof(unsigned long long));

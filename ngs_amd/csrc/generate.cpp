@@ -256,6 +256,7 @@ static int generate_write(ngsq_generate *g, int fd_one, int fd_two, uint64_t see
         for (int k = 0; k < 2; k++) {
             enc[k].h = static_cast<const unsigned long long *>(zhw.h) + k * DEFLATE_HOST_WORDS;
             enc[k].hdev = static_cast<unsigned long long *>(zhw.dev) + k * DEFLATE_HOST_WORDS;
+            enc[k].effort = c->bgzf_effort;
         }
         GHIP(hipEventCreate(&zev.e[0]));
         GHIP(hipEventCreate(&zev.e[1]));

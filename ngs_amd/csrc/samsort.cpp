@@ -44,7 +44,7 @@ int write_sorted(ngsq_ctx *c, const char *sam_path, int fd, uint64_t max_records
 
     // phase 1: every record written into a slab, nothing compressed.  (R's failures leave their message in R.err.)
     auto parse = [&]() -> int {
-        if (const int rc = R.begin(c->device, c->stream)) return rc;
+        if (const int rc = R.begin(c->device, c->stream, c->bgzf_effort)) return rc;
         if (!R.budget) // (before the parser's buffers are there, as the reserve is sized)
             if (const int rc = R.default_budget()) return rc;
         if (const int rc = P.begin()) return rc;

@@ -58,7 +58,7 @@ int ngsq_sam_write_bam(ngsq_ctx *c, const char *sam_path, int fd, uint64_t max_r
     } while (0)
     auto run = [&]() -> int {
         hipStream_t st = c->stream;
-        if (const int rc = Z.start(fd, c->device)) return rc; // (first: the writer pins its ring beside the first chunk's read)
+        if (const int rc = Z.start(fd, c->device, c->bgzf_effort)) return rc; // (first: the writer pins its ring beside the first chunk's read)
         if (const int rc = P.begin()) return rc;
         // the header's blocks, in front of the first record (as samtools writes them)
         SHIP(hipEventCreate(&ev.e[0]));

@@ -87,6 +87,7 @@ struct SortResident {
     enum Ev { EV_S0 = 0, EV_S1, EV_G0, EV_G1, EV_I0, EV_I1, EV_B0, EV_B1, EV_N };
 
     int device = 0;
+    uint32_t bgzf_effort = 0; // the context's (ngsq_bgzf_set_effort): what the sink's encoder runs at
     hipStream_t st = nullptr;
     // phase 1 fills these: record i of the input lies at d_addr[i], d_len[i] bytes, with the key d_key[i]
     DevArray<uint64_t> d_addr, d_key;
@@ -134,8 +135,9 @@ struct SortResident {
     int sunk(int rc) { return rc ? fail(rc, "%s", z.err.c_str()) : rc; } // a step of the sink: its message becomes this object's
 
     // the device (made current), the stream the drivers' kernels run on, the events, the word the host reads
-    int begin(int device_, hipStream_t stream) {
+    int begin(int device_, hipStream_t stream, uint32_t bgzf_effort_) {
         device = device_;
+        bgzf_effort = bgzf_effort_;
         SRHIP(hipSetDevice(device));
         st = drain.s = stream;
         SRHIP(hw.reserve(sizeof(unsigned long long)));
@@ -317,7 +319,7 @@ struct SortResident {
             ix.blocks_per_piece = deflate_blocks(piece_bytes);
             SRHIP(ix.d_table.reserve(pieces * ix.blocks_per_piece + 1));
         }
-        if (sunk(z.start(fd, device))) return code;
+        if (sunk(z.start(fd, device, bgzf_effort))) return code;
         // the header's blocks, in front of the first record (as samtools writes them)
         SRHIP(d_piece.reserve(std::max<uint64_t>(hs.size(), std::min(piece_bytes, total)) + DEFLATE_IN_SLACK));
         SRHIP(hipMemcpyAsync(d_piece.p, hs.data(), hs.size(), hipMemcpyHostToDevice, st));

@@ -326,6 +326,7 @@ GENERATE_PLAIN_ONE, GENERATE_PLAIN_TWO = 1, 2
 # ---- include/ngsq_bgzf.h ----------------------------------------------------------------------
 BGZF_BLOCK_INPUT = 65280
 BGZF_EOF = 1
+BGZF_EFFORT_NORMAL, BGZF_EFFORT_HIGH = 0, 1
 BGZF_EOF_BLOCK = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
 
 
@@ -552,6 +553,9 @@ PROTOTYPES = {
                                            C.POINTER(GenerateBgzfReport)]),
     # include/ngsq_bgzf.h
     "ngsq_bgzf_deflate_bound": (C.c_uint64, [C.c_uint64, C.c_uint32]),
+    "ngsq_bgzf_set_effort": (C.c_int, [ctx_p, C.c_uint32]),
+    "ngsq_bgzf_effort": (C.c_uint32, [ctx_p]),
+    "ngsq_bgzf_effort_candidates": (C.c_uint32, [C.c_uint32]),
     "ngsq_bgzf_deflate_device": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p, C.c_uint32, C.POINTER(BgzfDeflateReport)]),
     "ngsq_bgzf_inflate_device": (C.c_int, [ctx_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p, C.c_int]),
     # include/ngsq_comm.h

@@ -561,11 +561,23 @@ def bam_to_sam(path: str, out_path: str, device: int = 0, max_records: int = 0, 
             os.close(fd)
 
 
-def sam_to_bam(path: str, out_path: str, device: int = 0, max_records: int = 0, chunk_bytes: int = 0, lib=None) -> Dict[str, float]:
+BGZF_EFFORTS = {"normal": ffi.BGZF_EFFORT_NORMAL, "high": ffi.BGZF_EFFORT_HIGH}
+
+
+def _set_effort(lib, ctx, effort: str):
+    """`--gzip-effort` for every encoder launch of ctx (ngsq_bgzf_set_effort): "normal" or "high"."""
+    if effort not in BGZF_EFFORTS:
+        raise ValueError(f"effort {effort!r}: one of {sorted(BGZF_EFFORTS)}")
+    _check(lib.ngsq_bgzf_set_effort(ctx, BGZF_EFFORTS[effort]), ctx, lib)
+
+
+def sam_to_bam(path: str, out_path: str, device: int = 0, max_records: int = 0, chunk_bytes: int = 0, lib=None,
+               effort: str = "normal") -> Dict[str, float]:
     """`ngs convert --gzip device <SAM> <BAM>` in process (include/ngsq_samtext.h): the BAM of the SAM text at `path` written to
     out_path (created or truncated), the lines parsed and the BGZF blocks written on GPU `device`.  max_records: at most this
     many records (0: all; the command line maps `-n N` to max(N, 1)); chunk_bytes: text bytes per chunk (0: the library's
-    default).  Returns the report; NgsqError on an open failure, a refused header or a line without a record."""
+    default); effort: `--gzip-effort`.  Returns the report; NgsqError on an open failure, a refused header or a line without a
+    record."""
     lib = lib or ffi.load_library()
     why = C.create_string_buffer(1024)
     rc = lib.ngsq_sam_check_header(path.encode(), None, why, len(why))   # (before any GPU work, and before out_path exists)
@@ -577,6 +589,7 @@ def sam_to_bam(path: str, out_path: str, device: int = 0, max_records: int = 0, 
     ctx = ffi.ctx_p()
     _check(lib.ngsq_create(C.byref(cfg), C.byref(ctx)), None, lib)
     try:
+        _set_effort(lib, ctx, effort)
         fd = os.open(out_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o666)
         try:
             rep = ffi.SamTextReport()
@@ -598,12 +611,13 @@ def _index_report(rep, lib) -> Dict[str, float]:
 
 
 def sam_to_sorted_bam(path: str, out_path: str, device: int = 0, max_records: int = 0, chunk_bytes: int = 0, piece_bytes: int = 0,
-                      max_resident_bytes: int = 0, lib=None, bai_path: Optional[str] = None, index_tile_records: int = 0):
+                      max_resident_bytes: int = 0, lib=None, bai_path: Optional[str] = None, index_tile_records: int = 0,
+                      effort: str = "normal"):
     """`ngs convert --gzip device --sort coordinate <SAM> <BAM>` in process (include/ngsq_samtext.h, ngsq_sam_write_sorted_bam): as
     sam_to_bam, the records in coordinate order, unplaced ones last.  piece_bytes: sorted record bytes gathered and compressed at
     a time; max_resident_bytes: device memory the records may take (0 each: the library's defaults).  Returns the report.
     bai_path: `--write-index` (ngsq_sam_write_sorted_bam_indexed): the BAI of out_path is written there, index_tile_records sorted
-    records per launch of the index pass (0: the library's default); returns (sort report, index report)."""
+    records per launch of the index pass (0: the library's default); returns (sort report, index report).  effort: `--gzip-effort`."""
     lib = lib or ffi.load_library()
     why = C.create_string_buffer(1024)
     rc = lib.ngsq_sam_check_header(path.encode(), None, why, len(why))   # (before any GPU work, and before out_path exists)
@@ -615,6 +629,7 @@ def sam_to_sorted_bam(path: str, out_path: str, device: int = 0, max_records: in
     ctx = ffi.ctx_p()
     _check(lib.ngsq_create(C.byref(cfg), C.byref(ctx)), None, lib)
     try:
+        _set_effort(lib, ctx, effort)
         fd = os.open(out_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o666)
         try:
             rep = ffi.SamSortReport()
@@ -634,7 +649,7 @@ def sam_to_sorted_bam(path: str, out_path: str, device: int = 0, max_records: in
 
 def bam_to_sorted_bam(path: str, out_path: str, device: int = 0, max_records: int = 0, batch_records: int = 0, piece_bytes: int = 0,
                       max_resident_bytes: int = 0, lib=None, bai_path: Optional[str] = None, index_tile_records: int = 0,
-                      rounds: bool = False):
+                      rounds: bool = False, effort: str = "normal"):
     """`ngs convert --gzip device --sort coordinate <BAM> <BAM>` in process (include/ngsq_bamsort.h): the records of the BAM at
     `path`, in any order, written to out_path (created or truncated) in coordinate order, unplaced ones last, inflated, sorted
     and compressed on GPU `device`.  max_records: the first so many records are sorted (0: all; the command line maps `-n N` to
@@ -644,9 +659,11 @@ def bam_to_sorted_bam(path: str, out_path: str, device: int = 0, max_records: in
     bai_path: `--write-index` (ngsq_bam_write_sorted_bam_indexed): the BAI of out_path is written there, index_tile_records sorted
     records per launch of the index pass (0: the library's default); returns (sort report, index report).
     rounds: ngsq_bam_write_sorted_bam_rounds -- records beyond max_resident_bytes are no refusal: the input is walked again and
-    sorted in rounds, to the same bytes; returns (sort report, rounds report), or (sort report, index report, rounds report)."""
+    sorted in rounds, to the same bytes; returns (sort report, rounds report), or (sort report, index report, rounds report).
+    effort: `--gzip-effort`."""
     lib = lib or ffi.load_library()
     with _reader_and_plain_context(lib, path, device, "opening BAM input file: ") as (bam, ctx):
+        _set_effort(lib, ctx, effort)
         fd = os.open(out_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o666)
         try:
             rep = ffi.BamSortReport()
@@ -887,9 +904,10 @@ class Generator:
     Opening is host only and raises NgsqError on every up-front refusal; write() brings the FASTAs to GPU `device` the first
     time and writes pairs [first_pair, first_pair + n_pairs) to the two paths (created or truncated; append=True adds to them)."""
 
-    def __init__(self, providers, device: int = 0, lib=None):
+    def __init__(self, providers, device: int = 0, lib=None, effort: str = "normal"):
         self.lib = lib or ffi.load_library()
         self.device = device
+        self.effort = effort  # `--gzip-effort`: what the encoder of a BGZF output runs at
         self._g, self._ctx = C.c_void_p(), None
         self._paths = [str(p[0]).encode() for p in providers]
         arr = (ffi.GenerateProvider * max(len(providers), 1))()
@@ -914,6 +932,7 @@ class Generator:
             ctx = ffi.ctx_p()
             _check(self.lib.ngsq_create(C.byref(cfg), C.byref(ctx)), None, self.lib)
             self._ctx = ctx
+            _set_effort(self.lib, ctx, self.effort)
             _check_generate(self.lib.ngsq_generate_load(self._g, ctx), self.lib)
 
     def write_fds(self, fd_one: int, fd_two: int, seed: int, n_pairs: int, first_pair: int = 0, batch_pairs: int = 0,
@@ -963,15 +982,17 @@ class Generator:
 
 
 def generate(providers, path_one: str, path_two: str, seed: int, n_pairs: int, first_pair: int = 0, batch_pairs: int = 0, device: int = 0, lib=None,
-             bgzf: bool = False):
-    """One call of `ngs generate` in process: the report of Generator.write.  bgzf: both files are BGZF written on the device."""
-    with Generator(providers, device=device, lib=lib) as g:
+             bgzf: bool = False, effort: str = "normal"):
+    """One call of `ngs generate` in process: the report of Generator.write.  bgzf: both files are BGZF written on the device, at
+    `effort` (`--gzip-effort`)."""
+    with Generator(providers, device=device, lib=lib, effort=effort) as g:
         return g.write(path_one, path_two, seed, n_pairs, first_pair, batch_pairs, bgzf=bgzf)
 
 
-def bgzf_deflate(data, device: int = 0, eof: bool = True, lib=None):
+def bgzf_deflate(data, device: int = 0, eof: bool = True, lib=None, effort: str = "normal"):
     """(bytes, report): `data` as BGZF compressed on GPU `device` (include/ngsq_bgzf.h: ngsq_bgzf_deflate_device), blocks of
-    ffi.BGZF_BLOCK_INPUT input bytes, the EOF block behind them with eof."""
+    ffi.BGZF_BLOCK_INPUT input bytes, the EOF block behind them with eof.  effort: "normal", or "high" for a harder match search
+    (ngsq_bgzf_set_effort)."""
     lib = lib or ffi.load_library()
     data = bytes(data)
     flags = ffi.BGZF_EOF if eof else 0
@@ -981,6 +1002,7 @@ def bgzf_deflate(data, device: int = 0, eof: bool = True, lib=None):
     ctx = ffi.ctx_p()
     _check(lib.ngsq_create(C.byref(cfg), C.byref(ctx)), None, lib)
     try:
+        _set_effort(lib, ctx, effort)
         cap = lib.ngsq_bgzf_deflate_bound(len(data), flags)
         out = np.empty(max(cap, 1), np.uint8)
         n = C.c_uint64(0)
