@@ -5,16 +5,16 @@
 // This is the dominant kernel of the `ngs qc` scan: 150 of the 254 algorithmic
 // bytes per 150 bp record.  Two kernels (measurements: DESIGN.md section 4):
 //
-//  k_qual_perm  rows of up to 256 bytes.  thread = one 16-byte WINDOW (record, w) of
-//               a row, w fixed per thread; ONE v_perm_b32 per byte builds the LDS
+//  k_qual_perm  rows of up to 256 bytes.  thread = one 16-byte WINDOW of the buffer, aligned
+//               in memory, its cycles fixed per thread; ONE v_perm_b32 per byte builds the LDS
 //               address of its (cycle, score) cell; see the comment above the kernel.
-//  k_qual_win   rows of 257..320 bytes: the same window-per-thread shape with a [q][kb * RP + w] table
-//               and two VALU operations per byte.
+//  k_qual_win   rows of 257..320 bytes: thread = one 16-byte window (record, w) of a row, with a
+//               [q][kb * RP + w] table and two VALU operations per byte.
 //
 // Shared design points:
 //  * Consecutive lanes hold consecutive windows, so a wave's global_load_dwordx4
-//    covers 1 KiB of contiguous bytes (rows are dense: the load is unaligned by
-//    design, gfx950 serves it as one request per lane).
+//    covers 1 KiB of contiguous bytes (k_qual_win: rows are dense, so the load is unaligned
+//    by design; gfx950 serves it as one request per lane).
 //  * The LDS bank of an update depends only on the cycle -- never on the score --
 //    so skewed real-world score distributions cannot serialise the LDS atomics.
 //  * Lanes of different records in one wave hold the same window w; taking the
@@ -432,116 +432,184 @@ hipError_t launch_qual_ragged(const LaunchInfo &li, const DeviceState &st, const
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_qual_perm: rows of up to 256 bytes (R <= 16 windows).  One VALU operation per byte.
+// k_qual_perm: fixed-pitch rows of up to 256 bytes, any pitch P (a runtime value).  One v_perm_b32 per byte.
+//
+// Thread = one 16-byte window of the QUAL BUFFER, aligned to 16 bytes in memory -- not a window of a row.  The
+// tally needs the cycle of a byte, never its record, so a window that straddles two rows is no special case:
+// the cycle of byte j of a window whose first byte has cycle c0 is (c0 + j) mod P, and the wrap is the next
+// row.  The stream starts at the 16-byte boundary at or below `qual` (m = qual mod 16 bytes in front): every
+// load is an aligned global_load_dwordx4, every byte of the buffer is loaded once and tallied once.
+//
+// The pattern of cycles repeats every W = P / gcd(P, 16) windows (16 W / P rows: 75 windows over 8 rows at
+// P = 150).  A WAVE takes one slot of 64 windows -- 1 KiB, eight whole 128-byte lines -- of every super-row of
+// lcm(W, 64) windows (75 slots at P = 150), over one contiguous run of super-rows: waves g = 0, 1, .. of the grid
+// take slot g mod slots of run g / slots, so the waves of a block read neighbouring KiB.  The cycles of a lane's
+// window are then constants of the lane for the whole kernel, every block has sixteen full waves and every
+// wave's load is line-aligned.  Measured against a block of T = W * (1024 / W) threads that streams T
+// consecutive windows per pass (975 at P = 150: the last wave 15 lanes wide, wave chunks not line-aligned), and
+// against T = lcm(W, 8) * k (600, line-aligned passes, ten waves): profiles/r20_qual_aligned_ab.txt -- slots
+// 2.53 ms, T = 975 2.59-2.61, T = 600 2.69-2.71 on 100 M x 150 bp; slots kept, also the faster at 144 and 160.
 //
 // LDS table of 64 scores x 4 dword planes x 64 words (64 KiB, two blocks per CU):
-//     byte address(q, cycle c = 16 w + 4 d + k) = d * 16384 + q * 256 + w * 16 + k * 4
-// so the address of byte k of dword d is  { byte1 = the score, byte0 = w*16 + k*4 }  + immediate
-// d*16384: ONE v_perm_b32 assembles it from the data dword and a per-lane register holding the
-// four byte-0 values.  The bank, (w*4 + k) mod 32, never depends on the score.  Scores 64..93 (never
-// seen on this path's short-read rows in practice) and 0xFF cells take the exact path: LDS for
-// q < 64, a global atomic otherwise.
-// Lanes that hold the same window w in one wave are R lanes apart; each takes the four bytes of a
-// dword in an order rotated by (lane / R) & 3, a per-lane constant folded into the v_perm selectors,
-// so they never update the same table word in one instruction.
+//     byte address(q, cycle c) = (c >> 2 & 3) * 16384 + q * 256 + (c >> 4) * 16 + (c & 3) * 4
+// Byte 0 of the address depends only on the cycle: four per-lane registers hold it for the sixteen bytes of the
+// window.  Byte 1 is the score plus the plane in bits 6-7: one v_add_u32 per data dword with a per-lane
+// constant puts the planes of its four bytes there (no byte carries: the fast path has seen every score below
+// 64), then ONE v_perm_b32 per byte assembles the address; every ds_add at offset 0.  The bank,
+// (4 (c >> 4) + (c & 3)) mod 32, never depends on the score.  Windows with a byte >= 64 take the exact path:
+// 0xFF = no score at this cycle, scores 64..93 (never seen on this path's short-read rows in practice) to the
+// global counters, 94..254 to E_BAD_QUAL.
+// Byte order.  Lanes of one row hold cycles 16 apart: different banks (but for windows 8 apart).  Lanes of
+// different rows -- three or four rows in 32 lanes -- and lanes W apart, which hold the same cycles, would meet
+// in the same banks: step k of a dword takes the byte with (c - row - pos / W) & 3 == k, c and row being that
+// BYTE's, so the bytes a window holds of the next row go with that row.  One more v_perm_b32 per dword, with
+// a per-lane selector, puts the bytes into step order (24 vector operations per window with the four adds);
+// the sixteen address selectors stay constants.  A rotation by the row of the window's first byte alone
+// (20 operations) measured 0.03-0.04 ms slower, by pos / W alone 0.18 ms slower (same file).
+// The first window of a misaligned buffer and the last window of the buffer are never loaded as 16 bytes (the
+// load would reach outside the buffer): their owners tally the bytes that exist one by one.
 // ---------------------------------------------------------------------------------------------
-constexpr uint32_t QP_MAX_R = 16;
+constexpr uint32_t QP_MAX_PITCH = 256; // a cycle must fit the low byte of a table address
 constexpr uint32_t QP_LDS_BYTES = 64 * 1024;
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
 
-// threads per block: the largest multiple of R up to 1024, so a thread keeps its window index w
-__host__ __device__ constexpr uint32_t qp_threads(uint32_t R) { return R * (1024u / R); }
+// windows after which the cycles repeat: P / gcd(P, 16)
+static uint32_t qp_period(uint32_t pitch) {
+    const uint32_t low = pitch & (0u - pitch);
+    return pitch / (low < 16u ? low : 16u);
+}
+constexpr uint32_t QP_THREADS = 1024;
 
-// exact tally of one window (rare: a 0xFF cell, a score >= 64 or an invalid byte in it)
+// exact tally of bytes [j_lo, j_hi) of one window (rare: a 0xFF cell, a score >= 64 or an invalid byte in it, or
+// a window at an end of the buffer); c0 = cycle of byte 0 of the window
 static __device__ __noinline__ uint32_t qp_exact(u64 *__restrict__ qual_counters, uint32_t x0, uint32_t x1, uint32_t x2,
-                                                 uint32_t x3, uint32_t w, uint32_t nvalid) {
+                                                 uint32_t x3, uint32_t c0, uint32_t pitch, uint32_t j_lo, uint32_t j_hi) {
     const uint32_t x[4] = {x0, x1, x2, x3};
-    uint32_t bad = 0;
-    for (uint32_t j = 0; j < nvalid; j++) {
+    uint32_t bad = 0, c = (c0 + j_lo) % pitch;
+    for (uint32_t j = j_lo; j < j_hi; j++) {
         const uint32_t q = (x[j >> 2] >> (8 * (j & 3))) & 0xFFu;
         if (q < 64u) {
-            lds_u32 *cell = reinterpret_cast<lds_u32 *>((j >> 2) * 16384u + q * 256u + w * 16u + (j & 3u) * 4u);
+            lds_u32 *cell = reinterpret_cast<lds_u32 *>(((c >> 2) & 3u) * 16384u + q * 256u + (c >> 4) * 16u + (c & 3u) * 4u);
             __hip_atomic_fetch_add(cell, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         } else if (q <= NGSQ_MAX_SCORE) {
-            atomicAdd(&qual_counters[(uint64_t)(16u * w + j) * QUAL_BINS + q], (u64)1);
+            atomicAdd(&qual_counters[(uint64_t)c * QUAL_BINS + q], (u64)1);
         } else if (q != 0xFFu) { // 0xFF = no score at this cycle (ngsq.h), 94..254 = decode error
             bad += 1;
         }
+        c = c + 1 == pitch ? 0u : c + 1;
     }
     return bad;
 }
 
-template <uint32_t R, uint32_t D>
-__global__ __launch_bounds__(1024) void k_qual_perm(DeviceState st, const uint8_t *__restrict__ qual, uint64_t n_rec,
-                                                    uint32_t pitch) {
+__global__ __launch_bounds__(1024) void k_qual_perm(DeviceState st, const uint8_t *__restrict__ qual, uint64_t n_bytes,
+                                                    uint32_t pitch, uint32_t W) {
     NGSQ_FOREGROUND_WAVE();
-    static_assert(R >= 1 && R <= QP_MAX_R, "window index must fit the low byte of a table address");
-    constexpr uint32_t T = qp_threads(R), RPB = T / R; // records per pass of the block
-    constexpr uint32_t magicR = R == 1 ? 0u : (uint32_t)(((1ull << 32) + R - 1) / R);
     extern __shared__ uint32_t s_q[]; // the ONLY LDS object: table offsets are LDS addresses
     if (reinterpret_cast<uintptr_t>((lds_u32 *)s_q) != 0) __builtin_trap();
-    for (uint32_t i = threadIdx.x; i < QP_LDS_BYTES / 4; i += T) s_q[i] = 0;
+    constexpr uint32_t T = QP_THREADS;
+    const uint32_t t = threadIdx.x;
+    for (uint32_t i = t; i < QP_LDS_BYTES / 4; i += T) s_q[i] = 0;
     __syncthreads();
 
-    const uint32_t rem = pitch - 16u * (R - 1); // bytes of the last window that belong to the row
-    const uint32_t r0 = R == 1 ? threadIdx.x : __umulhi(threadIdx.x, magicR); // < RPB
-    const uint32_t w = threadIdx.x - r0 * R;
-    // each block streams one contiguous run of rows, RPB rows per pass
-    const uint64_t per = (n_rec + gridDim.x - 1) / gridDim.x;
-    const uint64_t lo = min(per * blockIdx.x, n_rec), hi = min(lo + per, n_rec);
-    const uint64_t step = (uint64_t)RPB * pitch;
-    const uint8_t *pf = qual + (lo + r0) * (uint64_t)pitch + 16u * w;
+    // the stream: 16-byte windows from the 16-byte boundary at or below `qual`; its first m bytes are not the buffer's
+    const uint32_t m = (uint32_t)(reinterpret_cast<uintptr_t>(qual) & 15u);
+    const uint8_t *const stream = qual - m;
+    const uint64_t n_str = m + n_bytes;
+    const uint64_t n_win = n_bytes ? (n_str + 15) / 16 : 0;
+    // this wave's slot of 64 windows in every super-row of lcm(W, 64) windows, and its run of super-rows; the
+    // launch has at least one wave per slot
+    const uint32_t w_low = W & (0u - W), n_slots = W / (w_low < 64u ? w_low : 64u);
+    const uint64_t stride = 64ull * n_slots;
+    const uint32_t g = blockIdx.x * (T / 64) + (t >> 6), n_runs = gridDim.x * (T / 64) / n_slots;
+    const uint32_t pos = 64u * (g % n_slots) + (t & 63u); // this lane's window of the super-row
+    const uint64_t n_sr = (n_win + stride - 1) / stride, per = (n_sr + n_runs - 1) / n_runs;
+    const uint64_t run = g / n_slots, lo_sr = min(per * run, n_sr), hi_sr = run < n_runs ? min(lo_sr + per, n_sr) : lo_sr;
+    const uint64_t first = lo_sr * stride + pos, hi = min(hi_sr * stride, n_win);
+    const uint4 *pf = reinterpret_cast<const uint4 *>(stream) + first;
     u64 *const qc = st.counters + st.off_qual;
 
-    // Lanes with the same w in a wave belong to consecutive records: rotate the byte order by the
-    // record.  Selector k = { 0, 0, data byte kk, cvec byte kk }.
-    uint32_t sel[4];
+    // per-lane constants: the cycle of byte 0 of every window of this thread, and for every dword d of the window
+    //   ord[d]   the order its bytes are taken in: step k takes the byte whose cycle and row give (c - row - pos / W) & 3
+    //            == k (see above); where two bytes of a dword want one step -- a row ends inside it -- the later one
+    //            takes a step that is free.  A v_perm selector: byte k = the data byte of step k.
+    //   addv[d]  the plane (c >> 2 & 3) << 6 of each data byte, added to its score (data order)
+    //   lowv[d]  the low address byte (c >> 4) * 16 + (c & 3) * 4 of each byte (step order)
+    const uint32_t c0 = (16u * pos + 16u * pitch - m) % pitch;
+    uint32_t ord[4], addv[4], lowv[4];
+    {
+        uint32_t c = c0, row = ((16u * (pos % W) + 16u * W - m) % (16u * W)) / pitch + pos / W;
 #pragma unroll
-    for (uint32_t k = 0; k < 4; k++) {
-        const uint32_t kk = (k + r0) & 3u;
-        sel[k] = 0x0C0C0000u | ((4u + kk) << 8) | kk;
+        for (uint32_t d = 0; d < 4; d++) {
+            uint32_t low = 0, taken = 0, late = 0; // steps taken, bytes still without one
+            ord[d] = addv[d] = 0;
+#pragma unroll
+            for (uint32_t b = 0; b < 4; b++) {
+                low |= ((c & 0xF0u) | ((c & 3u) << 2)) << (8 * b);
+                addv[d] |= ((c >> 2) & 3u) << (8 * b + 6);
+                const uint32_t k = (c - row) & 3u;
+                if (taken >> k & 1u) {
+                    late |= 1u << b;
+                } else {
+                    taken |= 1u << k;
+                    ord[d] |= b << (8 * k);
+                }
+                c += 1;
+                if (c == pitch) c = 0, row += 1;
+            }
+#pragma unroll
+            for (uint32_t b = 0; b < 4; b++) {
+                if (late >> b & 1u) {
+                    const uint32_t k = (uint32_t)__builtin_ctz(~taken);
+                    taken |= 1u << k;
+                    ord[d] |= b << (8 * k);
+                }
+            }
+            lowv[d] = __builtin_amdgcn_perm(low, low, ord[d]);
+        }
     }
-    // byte j = low address byte of byte j of a dword of window w
-    const uint32_t cvec = w * 0x10101010u + 0x0C080400u;
 
-    // passes of this thread; the very last window of the buffer is never loaded as 16 bytes (the
-    // load would run past the allocation): its owner stops one pass early and tallies it by bytes
-    uint32_t n_it = lo + r0 < hi ? (uint32_t)((hi - lo - r0 + RPB - 1) / RPB) : 0u;
-    const bool owns_last = n_it > 0 && w == R - 1 && lo + r0 + (uint64_t)(n_it - 1) * RPB == n_rec - 1;
+    // passes of this thread.  The last window of the buffer, and the first one where bytes in front of the buffer
+    // share it, are tallied by bytes below: their owner skips that pass here.
+    uint32_t n_it = first < hi ? (uint32_t)((hi - first + stride - 1) / stride) : 0u;
+    const bool owns_last = n_it > 0 && first + (uint64_t)(n_it - 1) * stride == n_win - 1;
+    const bool owns_first = m != 0 && n_it > 0 && first == 0;
     if (owns_last) n_it -= 1;
+    if (owns_first && n_it > 0) {
+        pf += stride;
+        n_it -= 1;
+    }
 
     uint32_t bad = 0;
     auto tally = [&](const uint4 &v) {
         // any byte >= 64 (bit 6 or 7)?  Then it may be 0xFF / a high or invalid score: exact path.
         const uint32_t any = (v.x | v.y | v.z | v.w) & 0xC0C0C0C0u;
         if (__builtin_expect(any == 0u, 1)) {
-            // Bytes of the last window that lie beyond the row are the next row's leading scores:
-            // they fall into cells of cycles >= pitch, which exist in the table but are never read back.
-            const uint32_t x[4] = {v.x, v.y, v.z, v.w};
+            // the plane into bits 6-7 of every score, the bytes into step order: two operations per dword
+            const uint32_t y[4] = {v.x + addv[0], v.y + addv[1], v.z + addv[2], v.w + addv[3]};
 #pragma unroll
             for (uint32_t d = 0; d < 4; d++) {
+                const uint32_t x = __builtin_amdgcn_perm(y[d], y[d], ord[d]);
 #pragma unroll
                 for (uint32_t k = 0; k < 4; k++) {
-                    // LDS address straight from the integer (the table starts at LDS offset 0)
-                    const uint32_t a = __builtin_amdgcn_perm(x[d], cvec, sel[k]);
-                    lds_u32 *cell = reinterpret_cast<lds_u32 *>(a) + d * 4096u;
-                    __hip_atomic_fetch_add(cell, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    // { 0, 0, data byte k, lowv byte k }: the LDS address straight from the integer (the table starts
+                    // at LDS offset 0)
+                    const uint32_t a = __builtin_amdgcn_perm(x, lowv[d], 0x0C0C0400u + 0x0101u * k);
+                    __hip_atomic_fetch_add(reinterpret_cast<lds_u32 *>(a), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
             }
         } else {
-            bad += qp_exact(qc, v.x, v.y, v.z, v.w, w, w == R - 1 ? rem : 16u);
+            bad += qp_exact(qc, v.x, v.y, v.z, v.w, c0, pitch, 0u, 16u);
         }
     };
     auto load = [&]() -> uint4 {
-        uint4 v;
-        __builtin_memcpy(&v, pf, 16); // one unaligned global_load_dwordx4
-        pf += step;
+        const uint4 v = *pf; // one aligned global_load_dwordx4
+        pf += stride;
         return v;
     };
 
-    // D windows in flight per thread.  Pass i lives in register slot i % (D+1): a load never targets
+    // D windows in flight per thread: depths 1..3 measured within 2 % of each other.  Pass i lives in register slot i % (D+1): a load never targets
     // the slot being tallied, so the compiler needs no copies (and no vmcnt(0)) to rotate them.
-    constexpr uint32_t NB = D + 1;
+    constexpr uint32_t D = 2, NB = D + 1;
     uint4 buf[NB];
 #pragma unroll
     for (uint32_t j = 0; j < D; j++)
@@ -562,56 +630,46 @@ __global__ __launch_bounds__(1024) void k_qual_perm(DeviceState st, const uint8_
         }
     }
 
-    if (owns_last) {
+    // the windows at the two ends of the buffer, byte by byte: stream bytes [s_lo, s_hi) of window g
+    auto edge = [&](uint64_t g, uint32_t j_lo, uint32_t j_hi) {
         uint32_t x[4] = {0, 0, 0, 0};
-        const uint64_t off = (n_rec - 1) * (uint64_t)pitch + 16u * (R - 1);
-        for (uint32_t k = 0; k < rem; k++) x[k >> 2] |= (uint32_t)qual[off + k] << (8 * (k & 3));
-        bad += qp_exact(qc, x[0], x[1], x[2], x[3], R - 1, rem);
-    }
+        for (uint32_t j = j_lo; j < j_hi; j++) x[j >> 2] |= (uint32_t)stream[16 * g + j] << (8 * (j & 3));
+        bad += qp_exact(qc, x[0], x[1], x[2], x[3], c0, pitch, j_lo, j_hi);
+    };
+    if (owns_last) edge(n_win - 1, n_win == 1 ? m : 0u, (uint32_t)(n_str - 16 * (n_win - 1)));
+    if (owns_first && n_win > 1) edge(0, m, 16u);
     __syncthreads();
-    // flush in table order (conflict-free reads): word i = d*4096 + q*64 + w*4 + k
-    for (uint32_t i = threadIdx.x; i < QP_LDS_BYTES / 4; i += T) {
+    // flush in table order (conflict-free reads): word i = d*4096 + q*64 + w*4 + k holds cycle 16 w + 4 d + k; the
+    // cells of cycles >= pitch were never touched
+    for (uint32_t i = t; i < QP_LDS_BYTES / 4; i += T) {
         const uint32_t v = s_q[i];
         if (v) {
             const uint32_t d = i >> 12, q = (i >> 6) & 63u, c = ((i >> 2) & 15u) * 16u + d * 4u + (i & 3u);
-            if (c < pitch) atomicAdd(&qc[(uint64_t)c * QUAL_BINS + q], (u64)v);
+            atomicAdd(&qc[(uint64_t)c * QUAL_BINS + q], (u64)v);
         }
     }
     uint32_t r = bad;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) r += __shfl_down(r, o, 64);
-    if ((threadIdx.x & 63) == 0 && r) atomicAdd(&st.counters[C_ERR + E_BAD_QUAL], (u64)r);
+    if ((t & 63) == 0 && r) atomicAdd(&st.counters[C_ERR + E_BAD_QUAL], (u64)r);
 }
 
-template <uint32_t R, uint32_t D>
 static hipError_t launch_perm(const LaunchInfo &li, const DeviceState &st, const DeviceBatch &b, hipStream_t s) {
     static bool attr = false;
     if (!attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_qual_perm<R, D>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_qual_perm),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)QP_LDS_BYTES);
         if (e != hipSuccess) return e;
         attr = true;
     }
-    constexpr uint32_t RPB = qp_threads(R) / R;
-    uint64_t g = (b.n + RPB - 1) / RPB;
+    const uint32_t W = qp_period(b.qual_stride), T = QP_THREADS;
+    const uint64_t n_bytes = b.n * (uint64_t)b.qual_stride;
+    const uint64_t n_win = (n_bytes + (reinterpret_cast<uintptr_t>(b.qual) & 15u) + 15) / 16;
+    uint64_t g = (n_win + T - 1) / T;
     if (g > (uint64_t)li.n_cu * 2) g = (uint64_t)li.n_cu * 2; // 64 KiB of LDS each: two blocks per CU
-    if (g < 1) g = 1;
-    hipLaunchKernelGGL((k_qual_perm<R, D>), dim3((uint32_t)g), dim3(qp_threads(R)), QP_LDS_BYTES, s, st, b.qual, b.n,
-                       b.qual_stride);
+    if (g < (W + 15) / 16) g = (W + 15) / 16; // a wave for every slot (at most W of them)
+    hipLaunchKernelGGL((k_qual_perm), dim3((uint32_t)g), dim3(T), QP_LDS_BYTES, s, st, b.qual, n_bytes, b.qual_stride, W);
     return hipGetLastError();
-}
-
-template <uint32_t D>
-static hipError_t dispatch_perm(uint32_t R, const LaunchInfo &li, const DeviceState &st, const DeviceBatch &b,
-                                hipStream_t s) {
-    switch (R) {
-#define CASE(r) \
-    case r: return launch_perm<r, D>(li, st, b, s);
-        CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) CASE(13)
-        CASE(14) CASE(15) CASE(16)
-#undef CASE
-    default: return hipErrorInvalidValue;
-    }
 }
 
 template <uint32_t R>
@@ -649,11 +707,8 @@ bool qual_window_supported(const DeviceState &st, const DeviceBatch &b) {
 }
 
 hipError_t launch_qual_window(const LaunchInfo &li, const DeviceState &st, const DeviceBatch &b, hipStream_t s) {
-    const uint32_t R = (b.qual_stride + 15) / 16;
-    // two windows in flight per thread: depths 1..3, one or two blocks per CU, nontemporal loads and a
-    // block-interleaved row order all measured within 2 % of each other
-    if (R <= QP_MAX_R) return dispatch_perm<2>(R, li, st, b, s);
-    return dispatch(R, li, st, b, s);
+    if (b.qual_stride <= QP_MAX_PITCH) return launch_perm(li, st, b, s);
+    return dispatch((b.qual_stride + 15) / 16, li, st, b, s);
 }
 
 } // namespace ngsq
