@@ -80,6 +80,34 @@ uint64_t ngsq_depth_tile_positions(uint64_t requested);
 int ngsq_bam_depth(ngsq_bam *bam, ngsq_ctx *ctx, int fd, const char *query, const char *bai_path, uint32_t exclude_flags,
                    uint32_t min_mapq, uint64_t batch_records, uint64_t coalesce_gap, uint64_t tile_positions, ngsq_depth_report *out);
 
+/* ---- intervals of a BED file: the host side of mean depth per interval (the command that reduces the
+ * depth over them is not part of this build yet) ---- */
+
+/* One interval: positions [start, end) of sequence ref (an index into the binary reference list), 0-based half-open,
+ * start < end <= the sequence's length. */
+typedef struct ngsq_depth_interval {
+    int32_t ref;
+    uint32_t start, end;
+} ngsq_depth_interval;
+
+/* Read the BED file `path` against the reference list of `bam` (opened by ngsq_bam_open): *intervals receives *n intervals in
+ * the file's order (NULL when there is none), to be released with ngsq_depth_free_intervals.  Host code; needs no GPU.
+ * Lines end in "\n", a trailing "\r" is dropped; empty lines and lines that begin with "#", "track" or "browser" are skipped.
+ * Fields are separated by tabs: name, start, end; further fields are ignored.  start and end are decimal digits without a sign,
+ * at most 2^31 - 1; end is clipped to the sequence's length L.  Intervals may overlap, nest, repeat and be unsorted.  A file
+ * without an interval is accepted.
+ * Errors (NGSQ_ERR_INVALID_ARGUMENT, ngsq_bam_last_error()): "opening BED file: <strerror> (os error N)", and, N the 1-based
+ * line number, checked in this order, "reading BED file: line N: " followed by
+ *   "expected at least 3 tab-separated fields, found K"
+ *   "invalid start '<text>': expected a decimal number of at most 2147483647"   (likewise "invalid end")
+ *   "start S is not below end E"
+ *   "sequence '<name>' is not in the header"
+ *   "start S lies at or beyond the end of '<name>' (L positions)"
+ *   "more than 2147483647 intervals"
+ * tests/depth_windows_model.py restates the reader. */
+int ngsq_depth_read_bed(const ngsq_bam *bam, const char *path, ngsq_depth_interval **intervals, uint64_t *n);
+void ngsq_depth_free_intervals(ngsq_depth_interval *intervals);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,7 @@ SOURCES = ["kernels.hip", "qual_kernel.hip", "fields_kernel.hip", "cov_scan.hip"
            "generate_kernel.hip", "generate_args.cpp", "generate_gzip.cpp", "generate.cpp",
            "samtext_kernel.hip", "samtext.cpp",
            "sort_kernel.hip", "sort.cpp", "samsort.cpp", "samsort_header.cpp", "bamsort.cpp",
-           "depth_kernel.hip", "depth.cpp"]
+           "depth_kernel.hip", "depth.cpp", "depth_bed.cpp"]
 HEADERS = ["kernels.h", "context.h", "comm.h", "mem_pool.h", "bam_reader.h", "ingest_consumer.h", "ingest_kernels.h", "bgzf.h", "bgzf_crc.h", "deflate_kernels.h", "../../include/ngsq_bgzf.h", "reference_kernels.h", "../../include/ngsq.h",
            "../../include/ngsq_reference.h", "../../include/ngsq_comm.h",
            "../../include/ngsq_shared.h", "../../include/ngsq_synth.h", "../../include/ngsq_bam.h", "../../include/ngsq_stage.h",

@@ -300,6 +300,10 @@ class DepthReport(C.Structure):
                 ("copy_ms", C.c_double), ("write_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class DepthInterval(C.Structure):
+    _fields_ = [("ref", C.c_int32), ("start", C.c_uint32), ("end", C.c_uint32)]
+
+
 # ---- include/ngsq_generate.h ------------------------------------------------------------------
 GENERATE_MAX_TABLE = 1 << 20
 GENERATE_MAX_ATTEMPTS = 1024
@@ -524,6 +528,8 @@ PROTOTYPES = {
     "ngsq_depth_tile_positions": (C.c_uint64, [C.c_uint64]),
     "ngsq_bam_depth": (C.c_int, [C.c_void_p, ctx_p, C.c_int, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
                                  C.c_uint64, C.POINTER(DepthReport)]),
+    "ngsq_depth_read_bed": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.POINTER(DepthInterval)), u64p]),
+    "ngsq_depth_free_intervals": (None, [C.POINTER(DepthInterval)]),
     # include/ngsq_generate.h
     "ngsq_generate_last_error": (C.c_char_p, []),
     "ngsq_generate_parse_provider": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(GenerateProvider), C.c_char_p, C.c_size_t]),

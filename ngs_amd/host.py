@@ -11,7 +11,7 @@ import ctypes as C
 import json
 import os
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -809,6 +809,31 @@ def bam_depth(path: str, out_path: str, query: Optional[str] = None, exclude_fla
             return {k: getattr(rep, k) for k, _ in ffi.DepthReport._fields_}
         finally:
             os.close(fd)
+
+
+def _read_bed(lib, bam, bed_path: str) -> List[Tuple[int, int, int]]:
+    """ngsq_depth_read_bed on an open reader: (sequence index, start, end) of every interval, in the file's order."""
+    iv, n = C.POINTER(ffi.DepthInterval)(), C.c_uint64()
+    _check_bam(lib.ngsq_depth_read_bed(bam, bed_path.encode(), C.byref(iv), C.byref(n)), lib)
+    try:
+        return [(iv[k].ref, iv[k].start, iv[k].end) for k in range(n.value)]
+    finally:
+        lib.ngsq_depth_free_intervals(iv)
+
+
+def depth_read_bed(path: str, bed_path: str, lib=None) -> List[Tuple[int, int, int]]:
+    """The intervals of the BED file bed_path against the reference list of the BAM `path`, in the file's
+    order: (sequence index, start, end), 0-based half-open, the end clipped to the sequence (ngsq_depth_read_bed).  Host only;
+    NgsqError with the line number for a line that is refused."""
+    lib = lib or ffi.load_library()
+    bam = C.c_void_p()
+    rc = lib.ngsq_bam_open(path.encode(), 1, C.byref(bam))
+    if rc != ffi.OK:
+        raise NgsqError(rc, (lib.ngsq_bam_last_error() or b"").decode("utf-8", "replace"))
+    try:
+        return _read_bed(lib, bam, bed_path)
+    finally:
+        lib.ngsq_bam_close(bam)
 
 
 def _c_strings(items: Sequence[bytes]):
