@@ -80,8 +80,7 @@ uint64_t ngsq_depth_tile_positions(uint64_t requested);
 int ngsq_bam_depth(ngsq_bam *bam, ngsq_ctx *ctx, int fd, const char *query, const char *bai_path, uint32_t exclude_flags,
                    uint32_t min_mapq, uint64_t batch_records, uint64_t coalesce_gap, uint64_t tile_positions, ngsq_depth_report *out);
 
-/* ---- intervals of a BED file: the host side of mean depth per interval (the command that reduces the
- * depth over them is not part of this build yet) ---- */
+/* ---- `ngs depth --by <N|BED>`: the mean depth per window or per interval of a BED file ---- */
 
 /* One interval: positions [start, end) of sequence ref (an index into the binary reference list), 0-based half-open,
  * start < end <= the sequence's length. */
@@ -107,6 +106,49 @@ typedef struct ngsq_depth_interval {
  * tests/depth_windows_model.py restates the reader. */
 int ngsq_depth_read_bed(const ngsq_bam *bam, const char *path, ngsq_depth_interval **intervals, uint64_t *n);
 void ngsq_depth_free_intervals(ngsq_depth_interval *intervals);
+
+/* What one call of ngsq_bam_depth_windows did. */
+typedef struct ngsq_depth_windows_report {
+    uint64_t records_scanned; /* records the device ingest handed out */
+    uint64_t records_counted; /* records that count, as in ngsq_depth_report; with intervals: of the whole file, whether or not
+                                 their sequence has an interval */
+    uint64_t lines;           /* lines written */
+    uint64_t text_bytes;      /* bytes written */
+    uint64_t sequences;       /* sequences (or the one region) with at least one line */
+    uint64_t depth_sum;       /* sum of all interval sums, modulo 2^64 */
+    uint64_t tiles;           /* tiles of tile_positions the reduce pass took */
+    uint64_t passes;          /* format passes: each sizes, scans and writes at most lines_per_pass lines and waits once */
+    uint64_t batches;         /* batches of the device ingest */
+    uint64_t ranges;          /* range walks (0 without a query) */
+    double scan_ms;           /* host time inside the device ingest's calls */
+    double add_ms;            /* GPU time of the order check and of the kernels that add or count the records */
+    double reduce_ms;         /* GPU time of the reduce pass: block sums, offsets, prefix sums, window or interval sums */
+    double format_ms;         /* GPU time of the size pass, its scan and the write pass */
+    double copy_ms;           /* GPU time of the device-to-host copies of the text */
+    double write_ms;          /* the writer thread's time inside write(2) */
+    double total_ms;          /* wall clock of the call */
+} ngsq_depth_windows_report;
+
+/* Write the mean depth of `bam` (opened by ngsq_bam_open, no batch read yet) per interval to fd, one line
+ * "<name>\t<start>\t<end>\t<mean>\n" each.  The depth of a position, the records that count, query, bai_path, exclude_flags,
+ * min_mapq, batch_records, coalesce_gap, tile_positions and the order rules are ngsq_bam_depth's.
+ * window >= 1 (at most 2^31 - 1): the windows [kN, min((k + 1)N, L)) of every sequence in header order, all of them also where
+ * no record counts ("0.00"); a sequence of length 0 gives no line.  With a query the windows stay aligned to position 0 and are
+ * clipped to [S-1, min(E, L)); an empty region gives no line and is no error.
+ * window == 0: the n_intervals intervals (NULL only with n_intervals == 0), each as ngsq_depth_read_bed gives it (ref in the
+ * reference list, start < end <= L): sequences in header order, within one the order given; a sequence without an interval
+ * gives no line, and its records are still counted.  Not with a query ("mean depth per BED interval cannot be combined with a
+ * query").  No interval at all: nothing is written, no record is read, every count is 0, and a query is not looked at (the header must
+ * still be sorted and the reader fresh).
+ * The mean is the sum of the interval's depths over its length with exactly two decimals, rounded half up, in integers:
+ * w = sum / len, r = sum % len, f = (100 r + len / 2) / len, and f == 100 carries into w.
+ * lines_per_pass: lines the format pass takes at a time (0: the default; rounded up to a block's 256 lines).  The bytes do not
+ * depend on it, nor on batch_records, tile_positions or coalesce_gap.
+ * Errors as ngsq_bam_depth; bad arguments, window and intervals together and intervals outside the file's sequences are
+ * NGSQ_ERR_INVALID_ARGUMENT before the header is looked at.  tests/depth_windows_model.py restates the bytes and the counts. */
+int ngsq_bam_depth_windows(ngsq_bam *bam, ngsq_ctx *ctx, int fd, uint32_t window, const ngsq_depth_interval *intervals, uint64_t n_intervals,
+                           const char *query, const char *bai_path, uint32_t exclude_flags, uint32_t min_mapq, uint64_t batch_records,
+                           uint64_t coalesce_gap, uint64_t tile_positions, uint64_t lines_per_pass, ngsq_depth_windows_report *out);
 
 #ifdef __cplusplus
 }

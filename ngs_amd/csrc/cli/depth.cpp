@@ -1,6 +1,7 @@
-// depth.cpp -- `ngs depth` (this build's own command, the reference has none): the per-base depth of a
-// coordinate-sorted BAM file, or of one region of it, as bedGraph text on stdout or in a file.  The records are read, added up,
-// run-length coded and formatted on the GPU by ngsq_bam_depth (include/ngsq_depth.h).
+// depth.cpp -- `ngs depth` (DESIGN.md sections 23 and 24; this build's own command, the reference has none): the per-base depth of
+// a coordinate-sorted BAM file, or of one region of it, as bedGraph text on stdout or in a file, or with --by <N|BED> its mean
+// per window or per interval of a BED file.  The records are read, added up, reduced and formatted on the GPU by ngsq_bam_depth
+// and ngsq_bam_depth_windows (include/ngsq_depth.h).
 #include <fcntl.h>
 
 #include <cerrno>
@@ -33,8 +34,8 @@ uint32_t int_value(const std::string &v, const char *name, unsigned long long ma
 // argv[at] is "depth".  Exit 0 on success, 1 on every error.
 int depth_main(int argc, char **argv, int at) {
     std::vector<std::string> pos;
-    std::string out_path;
-    bool to_file = false;
+    std::string out_path, by;
+    bool to_file = false, has_by = false;
     uint32_t exclude = NGSQ_DEPTH_EXCLUDE_FLAGS, min_mapq = 0;
     int device = 0;
     for (int i = at + 1; i < argc; i++) {
@@ -49,6 +50,9 @@ int depth_main(int argc, char **argv, int at) {
                             "Options:\n"
                             "  -o, --output <PATH>\n"
                             "          File the bedGraph text is written to, created or truncated [default: stdout]\n"
+                            "      --by <N|BED>\n"
+                            "          Write the mean depth of every window of N positions, or of every interval of the BED file, instead\n"
+                            "          (digits are a window size: write ./500 for a file of that name; a BED file not with [QUERY])\n"
                             "      --exclude-flags <INT>\n"
                             "          Records with any of these flag bits do not count [default: 1796]\n"
                             "      --min-mapq <INT>\n"
@@ -56,11 +60,15 @@ int depth_main(int argc, char **argv, int at) {
                             "      --device <N>\n"
                             "          GPU the depth is computed on [default: 0]\n\n"
                             "Lines: <name> <start> <end> <depth>, tab-separated, 0-based half-open, one per run of equal depth, zero included.\n"
+                            "With --by: <name> <start> <end> <mean>, one per window or interval, the mean with two decimals, rounded half up.\n"
                             "A record covers its alignment start to its alignment end, deletions and skips included.\n");
             return 0;
         } else if (s == "-o" || s == "--output") {
             out_path = option_value(argc, argv, &i, "--output <PATH>");
             to_file = true;
+        } else if (s == "--by") {
+            by = option_value(argc, argv, &i, "--by <N|BED>");
+            has_by = true;
         } else if (s == "--exclude-flags") {
             exclude = int_value(option_value(argc, argv, &i, "--exclude-flags <INT>"), "--exclude-flags <INT>", 65535);
         } else if (s == "--min-mapq") {
@@ -72,6 +80,15 @@ int depth_main(int argc, char **argv, int at) {
     }
     if (pos.empty()) bail("the following required arguments were not provided: <BAM>");
     if (pos.size() > 2) bail("unexpected argument '" + pos[2] + "' found");
+    // --by: decimal digits behind an optional '+' are a window size, anything else is the path of a BED file
+    uint32_t window = 0;
+    const size_t digits_at = !by.empty() && by[0] == '+' ? 1 : 0;
+    const bool by_bed = has_by && (by.size() == digits_at || by.find_first_not_of("0123456789", digits_at) != std::string::npos);
+    if (has_by && !by_bed) {
+        window = int_value(by, "--by <N|BED>", 2147483647);
+        if (!window) bail("invalid value '" + by + "' for '--by <N|BED>': window size must be at least 1");
+    }
+    if (by_bed && pos.size() > 1) bail("the argument '--by <BED>' cannot be used with '[QUERY]'");
     const std::string &src = pos[0];
     const std::string format = detect_format(src);
     if (format.empty()) bail("Not able to determine filetype for extension: " + extension_of(src));
@@ -85,6 +102,9 @@ int depth_main(int argc, char **argv, int at) {
         uint64_t n = 0;
         if (ngsq_bam_query_chunks(bam, nullptr, query, nullptr, nullptr, nullptr, nullptr, 0, &n) != NGSQ_OK) bail(ngsq_bam_last_error());
     }
+    ngsq_depth_interval *intervals = nullptr;
+    uint64_t n_intervals = 0;
+    if (by_bed && ngsq_depth_read_bed(bam, by.c_str(), &intervals, &n_intervals) != NGSQ_OK) bail(ngsq_bam_last_error());
     // (2) the device, then the output; a reader that goes away ends the command with the write's error, not with a signal
     ngsq_ctx *ctx = plain_context(bam, device);
     if (!ctx) bail(ngsq_last_global_error());
@@ -96,13 +116,24 @@ int depth_main(int argc, char **argv, int at) {
     }
     // (3) the depth
     ngsq_depth_report rep{};
-    const int rc = ngsq_bam_depth(bam, ctx, fd, query, nullptr, exclude, min_mapq, 0, 0, 0, &rep);
+    ngsq_depth_windows_report wrep{};
+    const int rc = has_by ? ngsq_bam_depth_windows(bam, ctx, fd, window, intervals, n_intervals, query, nullptr, exclude, min_mapq, 0, 0, 0, 0, &wrep)
+                          : ngsq_bam_depth(bam, ctx, fd, query, nullptr, exclude, min_mapq, 0, 0, 0, &rep);
+    ngsq_depth_free_intervals(intervals);
     std::string msg = rc ? ngsq_bam_last_error() : "";
     if (to_file && close(fd) != 0 && !rc) msg = "writing depth to stream: " + std::string(strerror(errno)) + " (os error " + std::to_string(errno) + ")";
     ngsq_destroy(ctx);
     ngsq_bam_close(bam);
     if (!msg.empty()) bail(msg);
-    if (g_level >= 3)
+    if (g_level >= 3 && has_by)
+        fprintf(stderr, "[ngs] depth: %llu of %llu records counted in %llu batches and %llu range walks; %llu lines of %llu sequences in %llu tiles and "
+                        "%llu format passes, depth sum %llu, %llu text bytes; ingest %.1f ms, add %.1f ms, reduce %.1f ms, format %.1f ms, copy %.1f ms, "
+                        "write %.1f ms, total %.1f ms\n",
+                (unsigned long long)wrep.records_counted, (unsigned long long)wrep.records_scanned, (unsigned long long)wrep.batches,
+                (unsigned long long)wrep.ranges, (unsigned long long)wrep.lines, (unsigned long long)wrep.sequences, (unsigned long long)wrep.tiles,
+                (unsigned long long)wrep.passes, (unsigned long long)wrep.depth_sum, (unsigned long long)wrep.text_bytes, wrep.scan_ms, wrep.add_ms,
+                wrep.reduce_ms, wrep.format_ms, wrep.copy_ms, wrep.write_ms, wrep.total_ms);
+    else if (g_level >= 3)
         fprintf(stderr, "[ngs] depth: %llu of %llu records counted in %llu batches and %llu range walks; %llu runs of %llu sequences in %llu tiles, "
                         "%llu text bytes; ingest %.1f ms, add %.1f ms, runs %.1f ms, format %.1f ms, copy %.1f ms, write %.1f ms, total %.1f ms\n",
                 (unsigned long long)rep.records_counted, (unsigned long long)rep.records_scanned, (unsigned long long)rep.batches,

@@ -1,6 +1,7 @@
 // depth_kernel.hip -- `ngs depth` on the device.
 //   k_depth_order   one thread per record: the coordinate order against the record in front, the batch's first and last sequence
 //   k_depth_add     one thread per record: filter, reference span of the resolved CIGAR, +1 / -1 into the difference array
+//   k_depth_count   one thread per record: the same filter alone, a ballot and one atomic a wave (sequences without an array, section 24)
 //   k_depth_sums    a tile of the array, DEPTH_GRANULE positions per block: the block's sum of differences and count of run starts
 //   k_depth_offsets one block: both turned into running values over the tile's blocks, from the carry of the tile in front
 //   k_depth_runs    the tile again: every run start's coordinate and depth, compacted behind the run held back
@@ -106,6 +107,17 @@ __global__ __launch_bounds__(BT) void k_depth_add(ngsq_batch b, const uint8_t *_
             }
         }
     }
+    const unsigned long long m = __ballot(counts);
+    if ((threadIdx.x & 63u) == 0 && m) (void)atomicAdd(&st->counted, (unsigned long long)__popcll(m));
+}
+
+// k_depth_add's test alone, for a sequence that has no difference array (`ngs depth --by`)
+__global__ __launch_bounds__(BT) void k_depth_count(ngsq_batch b, const uint8_t *__restrict__ keep, int32_t ref, uint32_t exclude, uint32_t min_mapq,
+                                                    DepthState *st) {
+    const uint64_t i = (uint64_t)blockIdx.x * BT + threadIdx.x;
+    bool counts = false;
+    if (i < b.n_records)
+        counts = b.ref_id[i] == ref && b.pos[i] >= 0 && ((uint32_t)b.flag[i] & exclude) == 0 && (uint32_t)b.mapq[i] >= min_mapq && (!keep || keep[i]);
     const unsigned long long m = __ballot(counts);
     if ((threadIdx.x & 63u) == 0 && m) (void)atomicAdd(&st->counted, (unsigned long long)__popcll(m));
 }
@@ -297,6 +309,14 @@ hipError_t launch_depth_add(const ngsq_batch &b, const uint8_t *keep, const Dept
     uint32_t blocks;
     if (!w.len || !grid_of(b.n_records, BT, &blocks)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_depth_add, dim3(blocks), dim3(BT), 0, s, b, keep, w, exclude_flags, min_mapq, state);
+    return hipGetLastError();
+}
+
+hipError_t launch_depth_count(const ngsq_batch &b, const uint8_t *keep, int32_t ref, uint32_t exclude_flags, uint32_t min_mapq, DepthState *state,
+                              hipStream_t s) {
+    uint32_t blocks;
+    if (!state || !b.ref_id || !b.pos || !b.flag || !b.mapq || !grid_of(b.n_records, BT, &blocks)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_depth_count, dim3(blocks), dim3(BT), 0, s, b, keep, ref, exclude_flags, min_mapq, state);
     return hipGetLastError();
 }
 

@@ -57,6 +57,12 @@ struct DepthWindow {
 hipError_t launch_depth_add(const ngsq_batch &b, const uint8_t *keep, const DepthWindow &w, uint32_t exclude_flags, uint32_t min_mapq,
                             DepthState *state, hipStream_t s);
 
+// Every record of the batch that passes k_depth_add's test for sequence `ref` (pos >= 0, no excluded flag, mapq >= min_mapq,
+// keep[i] != 0 when keep is given) adds 1 to state->counted: a sequence that has no difference array (`ngs depth --by`: no
+// interval, length 0).  hipErrorInvalidValue, and no launch, for a null pointer or an empty batch.
+hipError_t launch_depth_count(const ngsq_batch &b, const uint8_t *keep, int32_t ref, uint32_t exclude_flags, uint32_t min_mapq, DepthState *state,
+                              hipStream_t s);
+
 // the arrays of the run path, sized for the largest tile: bsum / bcnt [tile / DEPTH_GRANULE], rstart / rdepth [tile + 1], off [tile + 2]
 struct DepthTileArrays {
     int32_t *bsum;

@@ -304,6 +304,14 @@ class DepthInterval(C.Structure):
     _fields_ = [("ref", C.c_int32), ("start", C.c_uint32), ("end", C.c_uint32)]
 
 
+class DepthWindowsReport(C.Structure):
+    _fields_ = [("records_scanned", C.c_uint64), ("records_counted", C.c_uint64), ("lines", C.c_uint64), ("text_bytes", C.c_uint64),
+                ("sequences", C.c_uint64), ("depth_sum", C.c_uint64), ("tiles", C.c_uint64), ("passes", C.c_uint64),
+                ("batches", C.c_uint64), ("ranges", C.c_uint64),
+                ("scan_ms", C.c_double), ("add_ms", C.c_double), ("reduce_ms", C.c_double), ("format_ms", C.c_double),
+                ("copy_ms", C.c_double), ("write_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 # ---- include/ngsq_generate.h ------------------------------------------------------------------
 GENERATE_MAX_TABLE = 1 << 20
 GENERATE_MAX_ATTEMPTS = 1024
@@ -530,6 +538,8 @@ PROTOTYPES = {
                                  C.c_uint64, C.POINTER(DepthReport)]),
     "ngsq_depth_read_bed": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.POINTER(DepthInterval)), u64p]),
     "ngsq_depth_free_intervals": (None, [C.POINTER(DepthInterval)]),
+    "ngsq_bam_depth_windows": (C.c_int, [C.c_void_p, ctx_p, C.c_int, C.c_uint32, C.POINTER(DepthInterval), C.c_uint64, C.c_char_p, C.c_char_p,
+                                         C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(DepthWindowsReport)]),
     # include/ngsq_generate.h
     "ngsq_generate_last_error": (C.c_char_p, []),
     "ngsq_generate_parse_provider": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(GenerateProvider), C.c_char_p, C.c_size_t]),

@@ -821,6 +821,32 @@ def _read_bed(lib, bam, bed_path: str) -> List[Tuple[int, int, int]]:
         lib.ngsq_depth_free_intervals(iv)
 
 
+def bam_depth_windows(path: str, out_path: str, window: int = 0, intervals: Optional[Sequence[Tuple[int, int, int]]] = None, bed: Optional[str] = None,
+                      query: Optional[str] = None, exclude_flags: int = ffi.DEPTH_EXCLUDE_FLAGS, min_mapq: int = 0, batch_records: int = 0,
+                      coalesce_gap: int = 0, tile_positions: int = 0, lines_per_pass: int = 0, device: int = 0, lib=None) -> Dict[str, float]:
+    """`ngs depth --by <N|BED> <BAM> [QUERY]` in process (ngsq_bam_depth_windows, include/ngsq_depth.h): the mean depth of the
+    coordinate-sorted BAM `path` per window of `window` positions, or per interval -- `intervals` as (sequence index, start, end),
+    or the BED file `bed`, read through ngsq_depth_read_bed on the same open reader -- written to out_path (created or
+    truncated) as "<name> <start> <end> <mean>" lines, two decimals, rounded half up.  The filters and batch_records /
+    coalesce_gap / tile_positions are bam_depth's; lines_per_pass: lines the format pass takes at a time (0: the default); the
+    bytes do not depend on any of the four.  Returns the report; NgsqError as bam_depth, and for a BED line that is refused."""
+    lib = lib or ffi.load_library()
+    q = query.encode() if query is not None else None
+    with _reader_and_plain_context(lib, path, device) as (bam, ctx):
+        if bed is not None:
+            intervals = list(intervals or []) + _read_bed(lib, bam, bed)
+        iv = list(intervals or [])
+        arr = (ffi.DepthInterval * max(len(iv), 1))(*[ffi.DepthInterval(r, s, e) for r, s, e in iv])
+        fd = os.open(out_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o666)
+        try:
+            rep = ffi.DepthWindowsReport()
+            _check_bam(lib.ngsq_bam_depth_windows(bam, ctx, fd, window, arr if iv else None, len(iv), q, None, exclude_flags, min_mapq, batch_records,
+                                                  coalesce_gap, tile_positions, lines_per_pass, C.byref(rep)), lib)
+            return {k: getattr(rep, k) for k, _ in ffi.DepthWindowsReport._fields_}
+        finally:
+            os.close(fd)
+
+
 def depth_read_bed(path: str, bed_path: str, lib=None) -> List[Tuple[int, int, int]]:
     """The intervals of the BED file bed_path against the reference list of the BAM `path`, in the file's
     order: (sequence index, start, end), 0-based half-open, the end clipped to the sequence (ngsq_depth_read_bed).  Host only;

@@ -14,6 +14,12 @@ process into /dev/null:
   bound_ms       the larger of scan_ms and text_bytes / D2H_GBPS (the pinned rate of DESIGN.md section 13.5)
   *_gpu_ms       the report's split of the kernels' GPU time: add, runs, format; copy
   format_gbps    text_bytes over format_gpu_ms: what the size pass, its scan and the write pass reach together
+Then, in the same run and on the whole file, `ngs depth --by` at 500 and 1000 positions a window and over a
+BED file the tool makes (--bed-intervals intervals of 100 to 300 positions, spread over the file's sequences by their length):
+  by_ms          open, context and ngsq_bam_depth_windows (by_call_ms: the library call alone; for the BED leg the file is read
+                 outside the clock and handed over as a list)
+  by_over_depth  by_call_ms over the whole file's depth_call_ms of the same run
+  *_gpu_ms       the report's split: add, reduce (block sums, offsets, prefix sums, window or interval sums), format; copy
 Medians of --reps runs.  One JSON line on stdout."""
 from __future__ import annotations
 
@@ -53,6 +59,27 @@ def child(args):
         bare_scan_ms(lib, path)  # warm-up: the page cache, the process's block cache
         scans = [bare_scan_ms(lib, path)[0] for _ in range(args.reps)]
         out = {"scan_ms": round(med(scans), 1), "all_ms": [round(x, 1) for x in scans]}
+    elif args.child == "by":
+        intervals = None
+        if args.by == "bed":
+            write_bed(lib, path, args.bed, args.bed_intervals)
+            intervals = host.depth_read_bed(path, args.bed, lib=lib)
+        kw = dict(intervals=intervals) if intervals is not None else dict(window=int(args.by))
+        bare_scan_ms(lib, path)  # warm-up
+        walls, reps = [], []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            reps.append(host.bam_depth_windows(path, "/dev/null", lib=lib, **kw))
+            walls.append((time.perf_counter() - t0) * 1e3)
+        r0 = reps[0]
+        out = {"by": args.by, "intervals": len(intervals) if intervals is not None else None, "records_scanned": r0["records_scanned"],
+               "records_counted": r0["records_counted"], "lines": r0["lines"], "text_bytes": r0["text_bytes"], "sequences": r0["sequences"],
+               "depth_sum": r0["depth_sum"], "tiles": r0["tiles"], "passes": r0["passes"], "batches": r0["batches"],
+               "by_ms": round(med(walls), 1), "by_call_ms": round(med(r["total_ms"] for r in reps), 1),
+               "ingest_ms": round(med(r["scan_ms"] for r in reps), 1), "add_gpu_ms": round(med(r["add_ms"] for r in reps), 1),
+               "reduce_gpu_ms": round(med(r["reduce_ms"] for r in reps), 1), "format_gpu_ms": round(med(r["format_ms"] for r in reps), 1),
+               "copy_gpu_ms": round(med(r["copy_ms"] for r in reps), 1), "write_ms": round(med(r["write_ms"] for r in reps), 1),
+               "all_ms": {"by": [round(x, 1) for x in walls], "by_call": [round(r["total_ms"], 1) for r in reps]}}
     else:
         query = args.query or None
         chunks = host.bam_query_chunks(path, query, lib=lib)[3] if query else None
@@ -79,6 +106,24 @@ def child(args):
     print(json.dumps(out))
 
 
+def write_bed(lib, path, bed, n):
+    """Some n intervals of 100 to 300 positions over the sequences of the BAM `path`, by their length, in no order: host work."""
+    import numpy as np
+    bam = C.c_void_p()
+    assert lib.ngsq_bam_open(path.encode(), 1, C.byref(bam)) == 0
+    seqs = [(lib.ngsq_bam_ref_name(bam, r).decode(), lib.ngsq_bam_ref_len(bam, r)) for r in range(lib.ngsq_bam_n_refs(bam))]
+    lib.ngsq_bam_close(bam)
+    seqs = [(name, ln) for name, ln in seqs if ln > 300]
+    total = sum(ln for _, ln in seqs)
+    rng = np.random.default_rng(24)
+    with open(bed, "w") as f:
+        for name, ln in seqs:
+            k = max(1, round(n * ln / total))
+            starts = rng.integers(0, ln - 300, size=k)
+            lens = rng.integers(100, 301, size=k)
+            f.write("".join(f"{name}\t{s}\t{s + w}\n" for s, w in zip(starts.tolist(), lens.tolist())))
+
+
 def step(limit, *argv):
     """A child under its time limit; None: it failed (the run ends there)."""
     cmd = [sys.executable, os.path.abspath(__file__), *[str(a) for a in argv]]
@@ -101,7 +146,10 @@ def main():
     ap.add_argument("--dir", default=None, help="where the files go (default: a temporary directory, removed afterwards)")
     ap.add_argument("--out", default=None, help="also write the JSON here")
     ap.add_argument("--step-timeout", type=int, default=600, help="seconds a child may take")
-    ap.add_argument("--child", choices=["write", "scan", "depth"], default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--bed-intervals", type=int, default=200_000, help="intervals of the BED leg")
+    ap.add_argument("--child", choices=["write", "scan", "depth", "by"], default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--by", default="", help=argparse.SUPPRESS)
+    ap.add_argument("--bed", default="", help=argparse.SUPPRESS)
     ap.add_argument("--path", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--records", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--aligner", action="store_true", help=argparse.SUPPRESS)
@@ -133,6 +181,15 @@ def main():
                     break
                 entry[what] = got
                 print(f"[bench_depth] {label} {what}: {json.dumps(got)}", file=sys.stderr, flush=True)
+            for by in ("500", "1000", "bed") if ok else ():
+                got = step(args.step_timeout, "--child", "by", "--path", path, "--reps", args.reps, "--by", by, "--bed", os.path.join(tmp.name, f"{label}.bed"),
+                           "--bed-intervals", args.bed_intervals)
+                if got is None:
+                    ok = False
+                    break
+                got["by_over_depth"] = round(got["by_call_ms"] / entry["whole_file"]["depth_call_ms"], 2)
+                entry["by_" + by] = got
+                print(f"[bench_depth] {label} --by {by}: {json.dumps(got)}", file=sys.stderr, flush=True)
             result["files"][label] = entry
         if os.path.exists(path):
             os.remove(path)
