@@ -150,6 +150,53 @@ int ngsq_bam_depth_windows(ngsq_bam *bam, ngsq_ctx *ctx, int fd, uint32_t window
                            const char *query, const char *bai_path, uint32_t exclude_flags, uint32_t min_mapq, uint64_t batch_records,
                            uint64_t coalesce_gap, uint64_t tile_positions, uint64_t lines_per_pass, ngsq_depth_windows_report *out);
 
+/* ---- `ngs depth --by <N|BED> --thresholds <T[,T...]>`: positions at or above each depth, per interval ---- */
+
+/* The most thresholds one call takes. */
+#define NGSQ_DEPTH_MAX_THRESHOLDS 8
+
+/* What one call of ngsq_bam_depth_thresholds did: the fields of ngsq_depth_windows_report in their order, then the covered totals. */
+typedef struct ngsq_depth_thresholds_report {
+    uint64_t records_scanned;
+    uint64_t records_counted;
+    uint64_t lines;
+    uint64_t text_bytes;
+    uint64_t sequences;
+    uint64_t depth_sum;
+    uint64_t tiles;
+    uint64_t passes;
+    uint64_t batches;
+    uint64_t ranges;
+    double scan_ms;
+    double add_ms;
+    double reduce_ms;         /* with the count kernels: block counts, their offsets, window or interval counts */
+    double format_ms;
+    double copy_ms;
+    double write_ms;
+    double total_ms;
+    uint64_t covered[NGSQ_DEPTH_MAX_THRESHOLDS]; /* covered[k]: the sum of n_k over all lines written (below 2^62: a count is below
+                                                    2^31 and a source has fewer than 2^31 lines); entries from n_thresholds upward are 0 */
+} ngsq_depth_thresholds_report;
+
+/* ngsq_bam_depth_windows with K = n_thresholds more columns a line: "<name>\t<start>\t<end>\t<mean>\t<n_1>\t...\t<n_K>\n".  The
+ * first four columns are ngsq_bam_depth_windows' of the same call: the same intervals, the same order, the same mean.  n_k is
+ * the number of positions of the interval whose depth is at least thresholds[k], in decimal; the depth of a position is
+ * ngsq_bam_depth's, unchanged (the same filters, the same span, the same clip at L).  A sequence, region or interval without a
+ * counted record gives "0.00" and K zeros.  There is no header line.  Every rule of ngsq_bam_depth_windows about windows,
+ * regions and intervals holds word for word: windows aligned to position 0 and clipped to the region, intervals not with a
+ * query, the empty interval list and the empty region answered with zero counts.  The bytes follow from the file, the filters,
+ * the query, the window or the intervals and the thresholds alone: not from batch_records, tile_positions, lines_per_pass,
+ * coalesce_gap or the grid.
+ * thresholds: n_thresholds (1 to NGSQ_DEPTH_MAX_THRESHOLDS) depths, each from 1 to 2^31 - 1, strictly ascending.  A null list,
+ * a count of 0 or above 8, an element of 0 or above 2^31 - 1 and a list that is not strictly ascending are
+ * NGSQ_ERR_INVALID_ARGUMENT before the header is looked at, as is everything ngsq_bam_depth_windows refuses there; all other
+ * errors are ngsq_bam_depth_windows'.  ngsq_bam_depth_windows itself, its bytes and the kernels it launches do not change.
+ * tests/depth_thresholds_model.py restates the bytes and the counts. */
+int ngsq_bam_depth_thresholds(ngsq_bam *bam, ngsq_ctx *ctx, int fd, uint32_t window, const ngsq_depth_interval *intervals, uint64_t n_intervals,
+                              const uint32_t *thresholds, uint32_t n_thresholds, const char *query, const char *bai_path, uint32_t exclude_flags,
+                              uint32_t min_mapq, uint64_t batch_records, uint64_t coalesce_gap, uint64_t tile_positions, uint64_t lines_per_pass,
+                              ngsq_depth_thresholds_report *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,8 @@
 // depth.cpp -- `ngs depth` (DESIGN.md sections 23 and 24; this build's own command, the reference has none): the per-base depth of
 // a coordinate-sorted BAM file, or of one region of it, as bedGraph text on stdout or in a file, or with --by <N|BED> its mean
-// per window or per interval of a BED file.  The records are read, added up, reduced and formatted on the GPU by ngsq_bam_depth
-// and ngsq_bam_depth_windows (include/ngsq_depth.h).
+// per window or per interval of a BED file, and with --thresholds <T,...> beside each mean the positions at or above each depth
+// (section 25).  The records are read, added up, reduced and formatted on the GPU by ngsq_bam_depth, ngsq_bam_depth_windows and
+// ngsq_bam_depth_thresholds (include/ngsq_depth.h).
 #include <fcntl.h>
 
 #include <cerrno>
@@ -34,8 +35,8 @@ uint32_t int_value(const std::string &v, const char *name, unsigned long long ma
 // argv[at] is "depth".  Exit 0 on success, 1 on every error.
 int depth_main(int argc, char **argv, int at) {
     std::vector<std::string> pos;
-    std::string out_path, by;
-    bool to_file = false, has_by = false;
+    std::string out_path, by, thr_list;
+    bool to_file = false, has_by = false, has_thr = false;
     uint32_t exclude = NGSQ_DEPTH_EXCLUDE_FLAGS, min_mapq = 0;
     int device = 0;
     for (int i = at + 1; i < argc; i++) {
@@ -53,6 +54,9 @@ int depth_main(int argc, char **argv, int at) {
                             "      --by <N|BED>\n"
                             "          Write the mean depth of every window of N positions, or of every interval of the BED file, instead\n"
                             "          (digits are a window size: write ./500 for a file of that name; a BED file not with [QUERY])\n"
+                            "      --thresholds <T,...>\n"
+                            "          With --by: behind each mean, the number of the interval's positions whose depth is at least T, for each of\n"
+                            "          1 to 8 depths, comma-separated and strictly ascending (as in: 1,10,20,30)\n"
                             "      --exclude-flags <INT>\n"
                             "          Records with any of these flag bits do not count [default: 1796]\n"
                             "      --min-mapq <INT>\n"
@@ -61,6 +65,7 @@ int depth_main(int argc, char **argv, int at) {
                             "          GPU the depth is computed on [default: 0]\n\n"
                             "Lines: <name> <start> <end> <depth>, tab-separated, 0-based half-open, one per run of equal depth, zero included.\n"
                             "With --by: <name> <start> <end> <mean>, one per window or interval, the mean with two decimals, rounded half up.\n"
+                            "With --thresholds: <name> <start> <end> <mean> <n_1> ... <n_K>, n_k the positions of the interval at or above the k-th depth.\n"
                             "A record covers its alignment start to its alignment end, deletions and skips included.\n");
             return 0;
         } else if (s == "-o" || s == "--output") {
@@ -69,6 +74,9 @@ int depth_main(int argc, char **argv, int at) {
         } else if (s == "--by") {
             by = option_value(argc, argv, &i, "--by <N|BED>");
             has_by = true;
+        } else if (s == "--thresholds") {
+            thr_list = option_value(argc, argv, &i, "--thresholds <T,...>");
+            has_thr = true;
         } else if (s == "--exclude-flags") {
             exclude = int_value(option_value(argc, argv, &i, "--exclude-flags <INT>"), "--exclude-flags <INT>", 65535);
         } else if (s == "--min-mapq") {
@@ -89,6 +97,26 @@ int depth_main(int argc, char **argv, int at) {
         if (!window) bail("invalid value '" + by + "' for '--by <N|BED>': window size must be at least 1");
     }
     if (by_bed && pos.size() > 1) bail("the argument '--by <BED>' cannot be used with '[QUERY]'");
+    // --thresholds: 1 to 8 integers from 1 to 2^31 - 1, comma-separated, strictly ascending
+    uint32_t thresholds[NGSQ_DEPTH_MAX_THRESHOLDS] = {}, n_thresholds = 0;
+    if (has_thr) {
+        if (!has_by) bail("the following required arguments were not provided: --by <N|BED>");
+        const std::string what = "invalid value '" + thr_list + "' for '--thresholds <T,...>': ";
+        std::vector<uint32_t> t;
+        for (size_t a = 0;;) {
+            const size_t comma = thr_list.find(',', a);
+            const std::string element = thr_list.substr(a, comma == std::string::npos ? std::string::npos : comma - a);
+            t.push_back(int_value(element, "--thresholds <T,...>", 2147483647));
+            if (!t.back()) bail("invalid value '0' for '--thresholds <T,...>': a threshold must be at least 1");
+            if (comma == std::string::npos) break;
+            a = comma + 1;
+        }
+        if (t.size() > NGSQ_DEPTH_MAX_THRESHOLDS) bail(what + "at most 8 thresholds");
+        for (size_t k = 1; k < t.size(); k++)
+            if (t[k] <= t[k - 1]) bail(what + "thresholds must be strictly ascending");
+        n_thresholds = (uint32_t)t.size();
+        std::copy(t.begin(), t.end(), thresholds);
+    }
     const std::string &src = pos[0];
     const std::string format = detect_format(src);
     if (format.empty()) bail("Not able to determine filetype for extension: " + extension_of(src));
@@ -117,7 +145,10 @@ int depth_main(int argc, char **argv, int at) {
     // (3) the depth
     ngsq_depth_report rep{};
     ngsq_depth_windows_report wrep{};
-    const int rc = has_by ? ngsq_bam_depth_windows(bam, ctx, fd, window, intervals, n_intervals, query, nullptr, exclude, min_mapq, 0, 0, 0, 0, &wrep)
+    ngsq_depth_thresholds_report trep{};
+    const int rc = has_thr ? ngsq_bam_depth_thresholds(bam, ctx, fd, window, intervals, n_intervals, thresholds, n_thresholds, query, nullptr, exclude, min_mapq, 0,
+                                                       0, 0, 0, &trep)
+                   : has_by ? ngsq_bam_depth_windows(bam, ctx, fd, window, intervals, n_intervals, query, nullptr, exclude, min_mapq, 0, 0, 0, 0, &wrep)
                           : ngsq_bam_depth(bam, ctx, fd, query, nullptr, exclude, min_mapq, 0, 0, 0, &rep);
     ngsq_depth_free_intervals(intervals);
     std::string msg = rc ? ngsq_bam_last_error() : "";
@@ -125,13 +156,19 @@ int depth_main(int argc, char **argv, int at) {
     ngsq_destroy(ctx);
     ngsq_bam_close(bam);
     if (!msg.empty()) bail(msg);
+    std::string covered; // the -v line of a thresholds call: the K covered totals
+    if (has_thr) {
+        memcpy(&wrep, &trep, sizeof wrep); // (the thresholds report begins with the windows report's fields)
+        covered = ", covered";
+        for (uint32_t k = 0; k < n_thresholds; k++) covered += " " + std::to_string((unsigned long long)trep.covered[k]);
+    }
     if (g_level >= 3 && has_by)
         fprintf(stderr, "[ngs] depth: %llu of %llu records counted in %llu batches and %llu range walks; %llu lines of %llu sequences in %llu tiles and "
-                        "%llu format passes, depth sum %llu, %llu text bytes; ingest %.1f ms, add %.1f ms, reduce %.1f ms, format %.1f ms, copy %.1f ms, "
+                        "%llu format passes, depth sum %llu%s, %llu text bytes; ingest %.1f ms, add %.1f ms, reduce %.1f ms, format %.1f ms, copy %.1f ms, "
                         "write %.1f ms, total %.1f ms\n",
                 (unsigned long long)wrep.records_counted, (unsigned long long)wrep.records_scanned, (unsigned long long)wrep.batches,
                 (unsigned long long)wrep.ranges, (unsigned long long)wrep.lines, (unsigned long long)wrep.sequences, (unsigned long long)wrep.tiles,
-                (unsigned long long)wrep.passes, (unsigned long long)wrep.depth_sum, (unsigned long long)wrep.text_bytes, wrep.scan_ms, wrep.add_ms,
+                (unsigned long long)wrep.passes, (unsigned long long)wrep.depth_sum, covered.c_str(), (unsigned long long)wrep.text_bytes, wrep.scan_ms, wrep.add_ms,
                 wrep.reduce_ms, wrep.format_ms, wrep.copy_ms, wrep.write_ms, wrep.total_ms);
     else if (g_level >= 3)
         fprintf(stderr, "[ngs] depth: %llu of %llu records counted in %llu batches and %llu range walks; %llu runs of %llu sequences in %llu tiles, "

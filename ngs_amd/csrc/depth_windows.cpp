@@ -5,6 +5,9 @@
 // interval's end and takes off its start in whichever tile holds them.  One function writes lines: format_pass().  Windows with
 // records, the windows of a sequence or region without a record and BED intervals all reach the text through it, and it alone
 // reserves the text buffer, launches the write kernel and advances the byte and line counts.
+// ngsq_bam_depth_thresholds is the same driver with K >= 1 thresholds: beside P the reduce pass keeps C_k,
+// the count of positions at or above T_k, looked up and carried as P is, and a line has K more columns.  With K = 0 nothing of
+// it is reserved or launched.
 #include "../../include/ngsq_depth.h"
 
 #include "depth_run.h"
@@ -41,6 +44,14 @@ struct WindowsRun {
     DevArray<uint64_t> d_bP, d_P, d_sum;
     DepthWTileArrays arr{};
     DevArray<DepthWState> d_ws;
+    // thresholds (thr.k >= 1 only): the count arrays of the reduce pass, the counts of a tile's windows, of the intervals, the carries
+    DepthThresholds thr{};
+    DevArray<uint16_t> d_cin;
+    DevArray<uint32_t> d_bcnt, d_bC, d_cnt, d_accT;
+    DepthTTileArrays tarr{};
+    uint64_t cnt_stride = 0; // a row of d_cnt
+    DevArray<DepthTState> d_ts;
+    uint64_t covered[NGSQ_DEPTH_MAX_THRESHOLDS] = {};
     // the format pass
     DevArray<uint64_t> d_off;
     ScanScratch scan;
@@ -74,8 +85,25 @@ int WindowsRun::begin(ngsq_bam *bam, ngsq_ctx *ctx, int fd, uint64_t longest, ui
     for (auto &e : rev.e) BHIP(hipEventCreate(&e));
     BHIP(d_ws.reserve(1));
     BHIP(hipMemset(d_ws.p, 0, sizeof(DepthWState)));
-    BHIP(hw.reserve(DEPTHW_HOST_WORDS * sizeof(unsigned long long)));
-    memset(hw.h, 0, DEPTHW_HOST_WORDS * sizeof(unsigned long long));
+    const uint32_t host_words = thr.k ? DEPTHT_HOST_WORDS : DEPTHW_HOST_WORDS;
+    BHIP(hw.reserve(host_words * sizeof(unsigned long long)));
+    memset(hw.h, 0, host_words * sizeof(unsigned long long));
+    if (thr.k) { // sized by K: cin K x tile x 2 bytes, bcnt / bC K x blocks, cnt K x the windows a tile can end, accT K x intervals
+        BHIP(d_cin.reserve(thr.k * t));
+        BHIP(d_bcnt.reserve(thr.k * (t / DEPTH_GRANULE)));
+        BHIP(d_bC.reserve(thr.k * (t / DEPTH_GRANULE)));
+        tarr = DepthTTileArrays{d_cin.p, d_bcnt.p, d_bC.p, t, (uint32_t)(t / DEPTH_GRANULE)};
+        if (window) {
+            cnt_stride = t / window + 2;
+            BHIP(d_cnt.reserve(thr.k * cnt_stride));
+        }
+        BHIP(d_ts.reserve(1));
+        BHIP(hipMemset(d_ts.p, 0, sizeof(DepthTState)));
+        if (!sorted.empty()) {
+            BHIP(d_accT.reserve(thr.k * sorted.size()));
+            BHIP(hipMemset(d_accT.p, 0, thr.k * sorted.size() * sizeof(uint32_t)));
+        }
+    }
     if (!sorted.empty()) {
         BHIP(d_iv.reserve(sorted.size()));
         BHIP(d_acc.reserve(sorted.size()));
@@ -99,13 +127,18 @@ int WindowsRun::format_pass(uint32_t ref, const DepthLineSource &src, bool *more
     const char *const name = r.name_of(ref);
     unsigned long long *const hdev = static_cast<unsigned long long *>(hw.dev);
     const unsigned long long *const h = static_cast<const unsigned long long *>(hw.h);
+    // with thresholds, the counts of the source's lines: those of the tile's windows, or of the sequence's intervals
+    const DepthTLineSource tsrc = src.window ? DepthTLineSource{src, thr.k, d_cnt.p, cnt_stride}
+                                             : DepthTLineSource{src, thr.k, d_accT.p ? d_accT.p + first[ref] : nullptr, sorted.size()};
     for (uint64_t k0 = 0; k0 < src.count && *more; k0 += lines_per_pass) {
         const uint32_t m = (uint32_t)std::min<uint64_t>(lines_per_pass, src.count - k0);
         if ((uint64_t)m + 1 > d_off.cap) return ngsq_bam_fail(NGSQ_ERR_STATE, "a format pass of %u lines is larger than its offsets array", m);
         BHIP(hipEventRecord(r.ev.e[4], r.st));
-        WLAUNCH(launch_depthw_size(src, k0, m, nl, d_off.p, d_ws.p, r.st));
+        if (thr.k) WLAUNCH(launch_deptht_size(tsrc, k0, m, nl, d_off.p, d_ws.p, d_ts.p, r.st));
+        else WLAUNCH(launch_depthw_size(src, k0, m, nl, d_off.p, d_ws.p, r.st));
         BHIP(scan.exclusive_scan(d_off.p, (uint64_t)m + 1, r.st));
-        WLAUNCH(launch_depthw_total(d_off.p, m, d_ws.p, hdev, r.st));
+        if (thr.k) WLAUNCH(launch_deptht_total(d_off.p, m, thr.k, d_ws.p, d_ts.p, hdev, r.st));
+        else WLAUNCH(launch_depthw_total(d_off.p, m, d_ws.p, hdev, r.st));
         BHIP(hipEventRecord(r.ev.e[5], r.st));
         BHIP(hipEventSynchronize(r.ev.e[5]));
         float ms = 0;
@@ -114,12 +147,14 @@ int WindowsRun::format_pass(uint32_t ref, const DepthLineSource &src, bool *more
         r.add_times();
         const uint64_t bytes = h[0];
         rep.depth_sum = h[1];
+        for (uint32_t k = 0; k < thr.k; k++) covered[k] = h[DEPTHW_HOST_WORDS + k];
         rep.passes++;
-        if (bytes < (uint64_t)m * (nl + 10u)) return ngsq_bam_fail(NGSQ_ERR_STATE, "the size pass gave fewer bytes than its lines need");
+        if (bytes < (uint64_t)m * (nl + 10u + 2u * thr.k)) return ngsq_bam_fail(NGSQ_ERR_STATE, "the size pass gave fewer bytes than its lines need");
         if (const int rc = r.room(bytes, more)) return rc;
         if (!*more) break;
         BHIP(hipEventRecord(r.ev.e[6], r.st));
-        WLAUNCH(launch_depthw_write(r.d_text[r.slots.slot()].p + r.used, src, k0, m, name, nl, d_off.p, r.st));
+        if (thr.k) WLAUNCH(launch_deptht_write(r.d_text[r.slots.slot()].p + r.used, tsrc, k0, m, name, nl, d_off.p, r.st));
+        else WLAUNCH(launch_depthw_write(r.d_text[r.slots.slot()].p + r.used, src, k0, m, name, nl, d_off.p, r.st));
         BHIP(hipEventRecord(r.ev.e[7], r.st));
         r.write_pending = true;
         r.used += bytes;
@@ -140,14 +175,17 @@ int WindowsRun::window_final(bool *more) {
     const uint64_t n_iv = window ? 0 : n_intervals(ref);
     rep.sequences++;
     BHIP(hipMemsetAsync(d_ws.p, 0, DEPTHW_CARRY_BYTES, r.st));
+    if (thr.k) BHIP(hipMemsetAsync(d_ts.p, 0, DEPTHT_CARRY_BYTES, r.st));
     for (uint64_t t0 = 0; t0 < wn.len && *more; t0 += r.tile) {
         const uint32_t n = (uint32_t)std::min<uint64_t>(r.tile, wn.len - t0);
         const uint64_t origin = (uint64_t)wn.lo + t0, tile_end = origin + n;
         if (!reduce_open) BHIP(hipEventRecord(rev.e[0], r.st));
-        WLAUNCH(launch_depthw_prefix(wn, t0, n, arr, d_ws.p, r.st));
+        if (thr.k) WLAUNCH(launch_deptht_prefix(wn, t0, n, arr, tarr, thr, d_ws.p, d_ts.p, r.st));
+        else WLAUNCH(launch_depthw_prefix(wn, t0, n, arr, d_ws.p, r.st));
         rep.tiles++;
         if (!window) {
             WLAUNCH(launch_depthw_interval_acc(d_iv.p + first[ref], n_iv, arr.P, t0, n, d_acc.p + first[ref], r.st));
+            if (thr.k) WLAUNCH(launch_deptht_interval_acc(d_iv.p + first[ref], n_iv, tarr, thr.k, t0, n, d_accT.p + first[ref], sorted.size(), r.st));
             BHIP(hipEventRecord(rev.e[1], r.st));
             reduce_open = true;
             continue;
@@ -155,8 +193,10 @@ int WindowsRun::window_final(bool *more) {
         // the windows whose end lies in (origin, tile_end]: window kb is the first; the window's last end, hi, belongs to the last tile
         const uint64_t kb = origin / window;
         const uint64_t count = tile_end / window - kb + (tile_end == hi && hi % window ? 1 : 0);
-        if (count > d_sum.cap) return ngsq_bam_fail(NGSQ_ERR_STATE, "a tile ends more windows than its sums array holds");
+        if (count > d_sum.cap || (thr.k && count > cnt_stride)) return ngsq_bam_fail(NGSQ_ERR_STATE, "a tile ends more windows than its sums array holds");
         if (count) WLAUNCH(launch_depthw_window_sums(arr.P, origin, n, window, kb, (uint32_t)count, hi, d_sum.p, d_ws.p, r.st));
+        if (count && thr.k)
+            WLAUNCH(launch_deptht_window_counts(tarr, thr.k, origin, n, window, kb, (uint32_t)count, hi, d_cnt.p, cnt_stride, d_ts.p, r.st));
         BHIP(hipEventRecord(rev.e[1], r.st));
         reduce_open = true;
         if (!count) continue;
@@ -180,11 +220,10 @@ int WindowsRun::no_record(uint32_t ref, uint32_t lo, uint32_t hi, bool *more) {
     return format_pass(ref, src, more);
 }
 
-} // namespace
-
-extern "C" int ngsq_bam_depth_windows(ngsq_bam *b, ngsq_ctx *c, int fd, uint32_t window, const ngsq_depth_interval *intervals, uint64_t n_intervals,
-                                      const char *query, const char *bai_path, uint32_t exclude_flags, uint32_t min_mapq, uint64_t batch_records,
-                                      uint64_t coalesce_gap, uint64_t tile_positions, uint64_t lines_per_pass, ngsq_depth_windows_report *out) {
+// Both entries: thr.k == 0 is ngsq_bam_depth_windows; covered (thr.k >= 1) receives the covered totals.
+int windows_call(ngsq_bam *b, ngsq_ctx *c, int fd, uint32_t window, const ngsq_depth_interval *intervals, uint64_t n_intervals, const DepthThresholds &thr,
+                 const char *query, const char *bai_path, uint32_t exclude_flags, uint32_t min_mapq, uint64_t batch_records, uint64_t coalesce_gap,
+                 uint64_t tile_positions, uint64_t lines_per_pass, ngsq_depth_windows_report *out, uint64_t *covered) {
     if (!b || !c || fd < 0 || exclude_flags > 65535u || min_mapq > 255u || window > 2147483647u || (window && n_intervals) ||
         (!intervals && n_intervals) || n_intervals > 2147483647u)
         return ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "null or invalid argument");
@@ -211,6 +250,7 @@ extern "C" int ngsq_bam_depth_windows(ngsq_bam *b, ngsq_ctx *c, int fd, uint32_t
     WindowsRun p;
     DepthRun &r = p.r;
     p.window = window;
+    p.thr = thr;
     r.exclude = exclude_flags;
     r.min_mapq = min_mapq;
     r.batch_records = batch_records ? batch_records : DEPTH_BATCH_RECORDS;
@@ -263,5 +303,41 @@ extern "C" int ngsq_bam_depth_windows(ngsq_bam *b, ngsq_ctx *c, int fd, uint32_t
         out->write_ms = r.w.write_ms;
         out->total_ms = now_ms() - t_begin;
     }
+    for (uint32_t k = 0; k < thr.k; k++) covered[k] = p.covered[k];
     return NGSQ_OK;
+}
+
+} // namespace
+
+extern "C" int ngsq_bam_depth_windows(ngsq_bam *b, ngsq_ctx *c, int fd, uint32_t window, const ngsq_depth_interval *intervals, uint64_t n_intervals,
+                                      const char *query, const char *bai_path, uint32_t exclude_flags, uint32_t min_mapq, uint64_t batch_records,
+                                      uint64_t coalesce_gap, uint64_t tile_positions, uint64_t lines_per_pass, ngsq_depth_windows_report *out) {
+    return windows_call(b, c, fd, window, intervals, n_intervals, DepthThresholds{}, query, bai_path, exclude_flags, min_mapq, batch_records, coalesce_gap,
+                        tile_positions, lines_per_pass, out, nullptr);
+}
+
+static_assert(offsetof(ngsq_depth_thresholds_report, covered) == sizeof(ngsq_depth_windows_report), "the windows report's fields in their order, then covered");
+
+extern "C" int ngsq_bam_depth_thresholds(ngsq_bam *b, ngsq_ctx *c, int fd, uint32_t window, const ngsq_depth_interval *intervals, uint64_t n_intervals,
+                                         const uint32_t *thresholds, uint32_t n_thresholds, const char *query, const char *bai_path,
+                                         uint32_t exclude_flags, uint32_t min_mapq, uint64_t batch_records, uint64_t coalesce_gap, uint64_t tile_positions,
+                                         uint64_t lines_per_pass, ngsq_depth_thresholds_report *out) {
+    DepthThresholds thr{};
+    bool ok = thresholds && n_thresholds >= 1 && n_thresholds <= NGSQ_DEPTH_MAX_THRESHOLDS;
+    for (uint32_t k = 0; ok && k < n_thresholds; k++) {
+        ok = thresholds[k] >= 1 && thresholds[k] <= 2147483647u && (!k || thresholds[k] > thresholds[k - 1]);
+        thr.t[k] = thresholds[k];
+    }
+    if (!ok) return ngsq_bam_fail(NGSQ_ERR_INVALID_ARGUMENT, "null or invalid thresholds: 1 to 8 depths from 1 to 2147483647, strictly ascending");
+    thr.k = n_thresholds;
+    if (out) memset(out, 0, sizeof *out);
+    ngsq_depth_windows_report w{};
+    uint64_t covered[NGSQ_DEPTH_MAX_THRESHOLDS] = {};
+    const int rc = windows_call(b, c, fd, window, intervals, n_intervals, thr, query, bai_path, exclude_flags, min_mapq, batch_records, coalesce_gap,
+                                tile_positions, lines_per_pass, &w, covered);
+    if (out) {
+        memcpy(out, &w, sizeof w);
+        memcpy(out->covered, covered, sizeof covered);
+    }
+    return rc;
 }

@@ -312,6 +312,13 @@ class DepthWindowsReport(C.Structure):
                 ("copy_ms", C.c_double), ("write_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+DEPTH_MAX_THRESHOLDS = 8
+
+
+class DepthThresholdsReport(C.Structure):
+    _fields_ = DepthWindowsReport._fields_ + [("covered", C.c_uint64 * DEPTH_MAX_THRESHOLDS)]
+
+
 # ---- include/ngsq_generate.h ------------------------------------------------------------------
 GENERATE_MAX_TABLE = 1 << 20
 GENERATE_MAX_ATTEMPTS = 1024
@@ -540,6 +547,9 @@ PROTOTYPES = {
     "ngsq_depth_free_intervals": (None, [C.POINTER(DepthInterval)]),
     "ngsq_bam_depth_windows": (C.c_int, [C.c_void_p, ctx_p, C.c_int, C.c_uint32, C.POINTER(DepthInterval), C.c_uint64, C.c_char_p, C.c_char_p,
                                          C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(DepthWindowsReport)]),
+    "ngsq_bam_depth_thresholds": (C.c_int, [C.c_void_p, ctx_p, C.c_int, C.c_uint32, C.POINTER(DepthInterval), C.c_uint64, C.POINTER(C.c_uint32), C.c_uint32,
+                                            C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
+                                            C.POINTER(DepthThresholdsReport)]),
     # include/ngsq_generate.h
     "ngsq_generate_last_error": (C.c_char_p, []),
     "ngsq_generate_parse_provider": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(GenerateProvider), C.c_char_p, C.c_size_t]),

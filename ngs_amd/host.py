@@ -823,13 +823,16 @@ def _read_bed(lib, bam, bed_path: str) -> List[Tuple[int, int, int]]:
 
 def bam_depth_windows(path: str, out_path: str, window: int = 0, intervals: Optional[Sequence[Tuple[int, int, int]]] = None, bed: Optional[str] = None,
                       query: Optional[str] = None, exclude_flags: int = ffi.DEPTH_EXCLUDE_FLAGS, min_mapq: int = 0, batch_records: int = 0,
-                      coalesce_gap: int = 0, tile_positions: int = 0, lines_per_pass: int = 0, device: int = 0, lib=None) -> Dict[str, float]:
-    """`ngs depth --by <N|BED> <BAM> [QUERY]` in process (ngsq_bam_depth_windows, include/ngsq_depth.h): the mean depth of the
+                      coalesce_gap: int = 0, tile_positions: int = 0, lines_per_pass: int = 0, device: int = 0, lib=None,
+                      thresholds: Optional[Sequence[int]] = None) -> Dict[str, float]:
+    """`ngs depth --by <N|BED> [--thresholds T,...] <BAM> [QUERY]` in process (ngsq_bam_depth_windows, include/ngsq_depth.h): the mean depth of the
     coordinate-sorted BAM `path` per window of `window` positions, or per interval -- `intervals` as (sequence index, start, end),
     or the BED file `bed`, read through ngsq_depth_read_bed on the same open reader -- written to out_path (created or
     truncated) as "<name> <start> <end> <mean>" lines, two decimals, rounded half up.  The filters and batch_records /
     coalesce_gap / tile_positions are bam_depth's; lines_per_pass: lines the format pass takes at a time (0: the default); the
-    bytes do not depend on any of the four.  Returns the report; NgsqError as bam_depth, and for a BED line that is refused."""
+    bytes do not depend on any of the four.  thresholds: a list of 1 to 8 strictly ascending depths calls
+    ngsq_bam_depth_thresholds instead: every line gains, per depth, the number of the interval's positions at or above it, and
+    the report `covered`, a list of their K totals.  Returns the report; NgsqError as bam_depth, and for a BED line that is refused."""
     lib = lib or ffi.load_library()
     q = query.encode() if query is not None else None
     with _reader_and_plain_context(lib, path, device) as (bam, ctx):
@@ -839,6 +842,14 @@ def bam_depth_windows(path: str, out_path: str, window: int = 0, intervals: Opti
         arr = (ffi.DepthInterval * max(len(iv), 1))(*[ffi.DepthInterval(r, s, e) for r, s, e in iv])
         fd = os.open(out_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o666)
         try:
+            if thresholds is not None:
+                t = [int(x) for x in thresholds]
+                trep = ffi.DepthThresholdsReport()
+                _check_bam(lib.ngsq_bam_depth_thresholds(bam, ctx, fd, window, arr if iv else None, len(iv), (C.c_uint32 * max(len(t), 1))(*t), len(t), q, None,
+                                                         exclude_flags, min_mapq, batch_records, coalesce_gap, tile_positions, lines_per_pass, C.byref(trep)), lib)
+                out = {k: getattr(trep, k) for k, _ in ffi.DepthWindowsReport._fields_}
+                out["covered"] = list(trep.covered)[:len(t)]
+                return out
             rep = ffi.DepthWindowsReport()
             _check_bam(lib.ngsq_bam_depth_windows(bam, ctx, fd, window, arr if iv else None, len(iv), q, None, exclude_flags, min_mapq, batch_records,
                                                   coalesce_gap, tile_positions, lines_per_pass, C.byref(rep)), lib)

@@ -20,6 +20,11 @@ BED file the tool makes (--bed-intervals intervals of 100 to 300 positions, spre
                  outside the clock and handed over as a list)
   by_over_depth  by_call_ms over the whole file's depth_call_ms of the same run
   *_gpu_ms       the report's split: add, reduce (block sums, offsets, prefix sums, window or interval sums), format; copy
+Then the thresholds legs, each beside the plain `--by` leg of the same file in the same run: `--by 1000
+--thresholds 1,10,20,30` and the same BED with the same list (ngsq_bam_depth_thresholds):
+  thr_over_by         by_call_ms over the plain leg's by_call_ms
+  reduce_over_by      reduce_gpu_ms over the plain leg's: the reduce pass moves 16 + 2 K bytes a position where it moved 16
+  covered             the report's K totals: positions of all lines at or above each depth
 Medians of --reps runs.  One JSON line on stdout."""
 from __future__ import annotations
 
@@ -37,6 +42,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 D2H_GBPS = 56.0  # pinned device-to-host copies of 32 MiB
+THRESHOLDS = "1,10,20,30"  # the thresholds legs' list
 
 
 def child(args):
@@ -65,6 +71,8 @@ def child(args):
             write_bed(lib, path, args.bed, args.bed_intervals)
             intervals = host.depth_read_bed(path, args.bed, lib=lib)
         kw = dict(intervals=intervals) if intervals is not None else dict(window=int(args.by))
+        if args.thresholds:
+            kw["thresholds"] = [int(t) for t in args.thresholds.split(",")]
         bare_scan_ms(lib, path)  # warm-up
         walls, reps = [], []
         for _ in range(args.reps):
@@ -79,7 +87,10 @@ def child(args):
                "ingest_ms": round(med(r["scan_ms"] for r in reps), 1), "add_gpu_ms": round(med(r["add_ms"] for r in reps), 1),
                "reduce_gpu_ms": round(med(r["reduce_ms"] for r in reps), 1), "format_gpu_ms": round(med(r["format_ms"] for r in reps), 1),
                "copy_gpu_ms": round(med(r["copy_ms"] for r in reps), 1), "write_ms": round(med(r["write_ms"] for r in reps), 1),
-               "all_ms": {"by": [round(x, 1) for x in walls], "by_call": [round(r["total_ms"], 1) for r in reps]}}
+               "all_ms": {"by": [round(x, 1) for x in walls], "by_call": [round(r["total_ms"], 1) for r in reps],
+                          "reduce_gpu": [round(r["reduce_ms"], 2) for r in reps]}}
+        if args.thresholds:
+            out["thresholds"], out["covered"] = kw["thresholds"], r0["covered"]
     else:
         query = args.query or None
         chunks = host.bam_query_chunks(path, query, lib=lib)[3] if query else None
@@ -150,6 +161,7 @@ def main():
     ap.add_argument("--child", choices=["write", "scan", "depth", "by"], default=None, help=argparse.SUPPRESS)
     ap.add_argument("--by", default="", help=argparse.SUPPRESS)
     ap.add_argument("--bed", default="", help=argparse.SUPPRESS)
+    ap.add_argument("--thresholds", default="", help=argparse.SUPPRESS)
     ap.add_argument("--path", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--records", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--aligner", action="store_true", help=argparse.SUPPRESS)
@@ -190,6 +202,18 @@ def main():
                 got["by_over_depth"] = round(got["by_call_ms"] / entry["whole_file"]["depth_call_ms"], 2)
                 entry["by_" + by] = got
                 print(f"[bench_depth] {label} --by {by}: {json.dumps(got)}", file=sys.stderr, flush=True)
+            for by in ("1000", "bed") if ok else ():
+                got = step(args.step_timeout, "--child", "by", "--path", path, "--reps", args.reps, "--by", by, "--bed", os.path.join(tmp.name, f"{label}.bed"),
+                           "--bed-intervals", args.bed_intervals, "--thresholds", THRESHOLDS)
+                if got is None:
+                    ok = False
+                    break
+                base = entry["by_" + by]
+                got["by_over_depth"] = round(got["by_call_ms"] / entry["whole_file"]["depth_call_ms"], 2)
+                got["thr_over_by"] = round(got["by_call_ms"] / base["by_call_ms"], 2)
+                got["reduce_over_by"] = round(got["reduce_gpu_ms"] / base["reduce_gpu_ms"], 2) if base["reduce_gpu_ms"] > 0 else None
+                entry["by_" + by + "_thresholds"] = got
+                print(f"[bench_depth] {label} --by {by} --thresholds {THRESHOLDS}: {json.dumps(got)}", file=sys.stderr, flush=True)
             result["files"][label] = entry
         if os.path.exists(path):
             os.remove(path)
