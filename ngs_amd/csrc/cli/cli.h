@@ -1,6 +1,6 @@
 // cli.h -- what the commands of `ngs` share: the log, the error exit, option helpers, file-format sniffing, and the
-// reader plus facet-less context that `index`, `convert`, `derive`, `view` and `depth` walk a file with.  One file per command beside it:
-// qc.cpp, index.cpp, convert.cpp, derive.cpp, view.cpp, generate.cpp, depth.cpp; ngs_main.cpp dispatches.  The command line includes the library's public headers only.
+// reader plus facet-less context that `index`, `convert`, `derive`, `view`, `depth` and `fastq` walk a file with.  One file per command beside it:
+// qc.cpp, index.cpp, convert.cpp, derive.cpp, view.cpp, generate.cpp, depth.cpp, fastq.cpp; ngs_main.cpp dispatches.  The command line includes the library's public headers only.
 #pragma once
 
 #include <unistd.h>
@@ -27,6 +27,7 @@ int derive_main(int argc, char **argv, int at);
 int view_main(int argc, char **argv, int at);
 int generate_main(int argc, char **argv, int at);
 int depth_main(int argc, char **argv, int at);
+int fastq_main(int argc, char **argv, int at);
 
 inline int g_level = 2; // 0 off (-q), 2 info (default), 3 debug (-v)   src/main.rs:71-83
 

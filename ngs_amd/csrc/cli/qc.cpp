@@ -164,7 +164,9 @@ void usage() {
             "       ngs [-q|-v] convert [OPTIONS] <FROM> <TO>   Convert BAM to SAM, the text formatted on the GPU (BAM to SAM only in\n"
             "                                                   this build)\n"
             "       ngs [-q|-v] generate [OPTIONS] <-n <USIZE>|-c <USIZE>> <READ_ONES_FILE> <READ_TWOS_FILE> <REFERENCE_PROVIDERS>...\n"
-            "                                                   Paired FASTQ reads sampled from reference FASTAs, drawn and written on the GPU\n");
+            "                                                   Paired FASTQ reads sampled from reference FASTAs, drawn and written on the GPU\n"
+            "       ngs [-q|-v] fastq [OPTIONS] <BAM> <READ_ONES_FILE> [<READ_TWOS_FILE>]\n"
+            "                                                   The reads of a BAM back as FASTQ, formatted on the GPU\n");
 }
 
 #define CHECK(ctx, expr)                                                                                   \
@@ -279,7 +281,7 @@ bool parse_args(int argc, char **argv, Args *out, int *status) {
     }
     if (!saw_qc) {
         usage();
-        bail("this build provides the `qc`, `index`, `convert`, `derive instrument`, `view` and `generate` subcommands only");
+        bail("this build provides the `qc`, `index`, `convert`, `derive instrument`, `view`, `generate`, `depth` and `fastq` subcommands only");
     }
     if (pos.size() != 2) {
         usage();

@@ -561,6 +561,36 @@ def bam_to_sam(path: str, out_path: str, device: int = 0, max_records: int = 0, 
             os.close(fd)
 
 
+def bam_to_fastq(path: str, path_one: str, path_two: Optional[str] = None, path_other: Optional[str] = None, device: int = 0,
+                 exclude_flags: int = ffi.FASTQ_EXCLUDE_FLAGS, require_flags: int = 0, name_suffix: bool = False,
+                 default_quality: int = ffi.FASTQ_DEFAULT_QUALITY, bgzf_mask: int = 0, max_records: int = 0, batch_records: int = 0,
+                 effort: str = "normal", lib=None) -> Dict[str, object]:
+    """`ngs fastq` in process (include/ngsq_fastq.h): the reads of the BAM `path` written as FASTQ to path_one (created or
+    truncated), or split by the flag into path_one, path_two and path_other (None with path_two: others are dropped), formatted
+    on GPU `device` from the device ingest.  bgzf_mask: bit 0 / 1 / 2: that output is BGZF from the device encoder at `effort`.
+    max_records: examine only that many records (0: all); batch_records: records per ingest batch (0: the library's default).
+    Returns the report, its three-entry arrays as lists; NgsqError on an open failure, a refused argument or a kept record with
+    a quality score above 93."""
+    lib = lib or ffi.load_library()
+    with _reader_and_plain_context(lib, path, device, "opening BAM input file: ") as (bam, ctx):
+        _set_effort(lib, ctx, effort)
+        fds = []
+        try:
+            for p in (path_one, path_two, path_other):
+                fds.append(-1 if p is None else os.open(p, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o666))
+            opt = ffi.FastqOptions()
+            opt.struct_size = C.sizeof(ffi.FastqOptions)
+            opt.require_flags, opt.exclude_flags, opt.default_quality = require_flags, exclude_flags, default_quality
+            opt.name_suffix, opt.bgzf_mask, opt.max_records, opt.batch_records = int(name_suffix), bgzf_mask, max_records, batch_records
+            rep = ffi.FastqReport()
+            _check_bam(lib.ngsq_bam_write_fastq(bam, ctx, fds[0], fds[1], fds[2], C.byref(opt), C.byref(rep)), lib)
+            return {k: (list(getattr(rep, k)) if k in ("text_bytes", "compressed_bytes") else getattr(rep, k)) for k, _ in ffi.FastqReport._fields_}
+        finally:
+            for fd in fds:
+                if fd >= 0:
+                    os.close(fd)
+
+
 BGZF_EFFORTS = {"normal": ffi.BGZF_EFFORT_NORMAL, "high": ffi.BGZF_EFFORT_HIGH}
 
 
