@@ -14,7 +14,7 @@
  * fd_one.  In two-file mode read ones go to fd_one, read twos to fd_two, and others to fd_other, or, with fd_other < 0, nowhere:
  * they are dropped and counted (dropped_other).  The order within every output is file order.  Nothing is paired or collated:
  * the two files of a name-grouped BAM correspond line by line, those of a coordinate-sorted BAM hold the same reads in
- * different orders.
+ * different orders.  `ngs fastq --collate` (ngsq_collate.h) pairs the mates by name on the GPU, whatever the order of the file.
  *
  * What is written for a kept record: four lines,
  *

@@ -5,6 +5,7 @@
 
 #include <unistd.h>
 
+#include <cerrno>
 #include <chrono>
 #include <cstdarg>
 #include <cstdio>
@@ -70,6 +71,25 @@ inline void logf(int level, const char *fmt, ...) {
 inline std::string option_value(int argc, char **argv, int *i, const char *name) {
     if (*i + 1 >= argc) bail(std::string("a value is required for '") + name + "' but none was supplied");
     return argv[++*i];
+}
+
+// a size: decimal digits with an optional K, M or G, powers of 1024 (as `samtools sort -m` reads its value), at least one byte;
+// `name` names the option in the message
+inline unsigned long long size_value(const std::string &v, const char *name) {
+    const std::string what = "invalid value '" + v + "' for '" + name + "': ";
+    size_t d = 0;
+    while (d < v.size() && v[d] >= '0' && v[d] <= '9') d++;
+    if (!d) bail(what + "a size is decimal digits with an optional K, M or G suffix");
+    unsigned shift = 0;
+    if (d + 1 == v.size() && (v[d] == 'K' || v[d] == 'k')) shift = 10;
+    else if (d + 1 == v.size() && (v[d] == 'M' || v[d] == 'm')) shift = 20;
+    else if (d + 1 == v.size() && (v[d] == 'G' || v[d] == 'g')) shift = 30;
+    else if (d != v.size()) bail(what + "a size is decimal digits with an optional K, M or G suffix");
+    errno = 0;
+    const unsigned long long digits = strtoull(v.substr(0, d).c_str(), nullptr, 10);
+    if (errno || digits > (~0ull >> shift)) bail(what + "number too large to fit in target type");
+    if (!digits) bail(what + "a size is at least one byte");
+    return digits << shift;
 }
 
 inline std::string with_commas(unsigned long long v) { // num_format Locale::en

@@ -113,22 +113,7 @@ bool parse_args(int argc, char **argv, int at, ConvertArgs *a) {
         } else if (s == "--write-index") {
             a->write_index = true;
         } else if (s == "--sort-memory") {
-            // decimal digits with an optional K, M or G, powers of 1024 (as `samtools sort -m` reads its value)
-            const std::string v = val("--sort-memory <SIZE>");
-            const std::string what = "invalid value '" + v + "' for '--sort-memory <SIZE>': ";
-            size_t d = 0;
-            while (d < v.size() && v[d] >= '0' && v[d] <= '9') d++;
-            if (!d) bail(what + "a size is decimal digits with an optional K, M or G suffix");
-            unsigned shift = 0;
-            if (d + 1 == v.size() && (v[d] == 'K' || v[d] == 'k')) shift = 10;
-            else if (d + 1 == v.size() && (v[d] == 'M' || v[d] == 'm')) shift = 20;
-            else if (d + 1 == v.size() && (v[d] == 'G' || v[d] == 'g')) shift = 30;
-            else if (d != v.size()) bail(what + "a size is decimal digits with an optional K, M or G suffix");
-            errno = 0;
-            const unsigned long long digits = strtoull(v.substr(0, d).c_str(), nullptr, 10);
-            if (errno || digits > (~0ull >> shift)) bail(what + "number too large to fit in target type");
-            if (!digits) bail(what + "a size is at least one byte");
-            a->sort_memory = digits << shift;
+            a->sort_memory = size_value(val("--sort-memory <SIZE>"), "--sort-memory <SIZE>");
             a->has_sort_memory = true;
         } else if (!s.empty() && s[0] == '-' && s != "-") bail("unexpected argument '" + s + "' found");
         else a->pos.push_back(s);

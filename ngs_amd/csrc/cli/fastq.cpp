@@ -1,13 +1,17 @@
 // fastq.cpp -- `ngs fastq` (this build's own command, the reference has none): the reads of a BAM file
 // back as FASTQ, in one file or split into read ones, read twos and others by the flag.  The records are read, classified
 // and formatted on the GPU by ngsq_bam_write_fastq (include/ngsq_fastq.h); gzipped outputs are compressed by host threads
-// behind a pipe or, with --gzip device, written as BGZF by the GPU's encoder, as `ngs generate` writes its files.
+// behind a pipe or, with --gzip device, written as BGZF by the GPU's encoder, as `ngs generate` writes its files.  With --collate
+// the mates are paired by name on the GPU (ngsq_bam_write_fastq_collated, include/ngsq_collate.h): the two
+// files pair line by line whatever the order of the BAM, and a fourth output takes the singletons.
 #include <fcntl.h>
 #include <sys/stat.h>
 
+#include <algorithm>
 #include <cerrno>
 
 #include "../../../include/ngsq_bgzf.h"
+#include "../../../include/ngsq_collate.h"
 #include "../../../include/ngsq_fastq.h"
 #include "../../../include/ngsq_generate.h"
 #include "cli.h"
@@ -62,9 +66,9 @@ bool same_file(const std::string &a, const std::string &b) {
 // argv[at] is "fastq".  Exit 0 on success, 1 on every error.
 int fastq_main(int argc, char **argv, int at) {
     std::vector<std::string> pos;
-    std::string other_path;
-    bool has_other = false, has_n = false, gzip_device = false, has_effort = false;
-    unsigned long long n = 0;
+    std::string other_path, single_path;
+    bool has_other = false, has_n = false, gzip_device = false, has_effort = false, collate = false, has_single = false, has_memory = false;
+    unsigned long long n = 0, collate_memory = 0;
     ngsq_fastq_options opt{};
     opt.struct_size = sizeof opt;
     opt.exclude_flags = NGSQ_FASTQ_EXCLUDE_FLAGS;
@@ -86,6 +90,15 @@ int fastq_main(int argc, char **argv, int at) {
                     "      --other <FILE>\n"
                     "          With <READ_TWOS_FILE>: destination for the reads that are neither a read one nor a read two (flag bits\n"
                     "          0x40 and 0x80 both clear or both set) [default: they are dropped and counted]\n"
+                    "      --collate\n"
+                    "          Pair the mates by name on the GPU, whatever the order of the BAM: pair p's read one is record p of\n"
+                    "          <READ_ONES_FILE> and its read two record p of <READ_TWOS_FILE> (without <READ_TWOS_FILE>: interleaved), in\n"
+                    "          the order of each pair's earlier record; reads without exactly one mate are singletons\n"
+                    "      --singletons <FILE>\n"
+                    "          With --collate: destination for the singletons [default: they are dropped and counted]\n"
+                    "      --collate-memory <SIZE>\n"
+                    "          With --collate: device memory the kept records may take, digits with an optional K, M or G\n"
+                    "          [default: the free memory less 4G]\n"
                     "      --exclude-flags <INT>\n"
                     "          Records with any of these flag bits are not written [default: 2304]\n"
                     "      --require-flags <INT>\n"
@@ -109,13 +122,22 @@ int fastq_main(int argc, char **argv, int at) {
                     "Outputs are FASTQ (.fastq, .fq) or gzipped FASTQ (.fastq.gz, .fq.gz).  A record becomes @<name>, its bases, +, its\n"
                     "qualities; a record on the reverse strand (flag 0x10) is reverse-complemented and its qualities reversed, so that the\n"
                     "read comes out as the sequencer gave it.  Secondary and supplementary records are left out by default.\n"
-                    "Nothing is paired: every file holds its reads in the order of the BAM.  The two files of a name-grouped BAM correspond\n"
-                    "line by line; those of a coordinate-sorted BAM hold the same reads in different orders -- group it by name first.\n",
+                    "Nothing is paired unless --collate is given: every file holds its reads in the order of the BAM.  The two files of a\n"
+                    "name-grouped BAM correspond line by line; those of a coordinate-sorted BAM hold the same reads in different orders --\n"
+                    "group it by name first, or give --collate.\n",
                     USAGE);
             return 0;
         } else if (s == "--other") {
             other_path = val("--other <FILE>");
             has_other = true;
+        } else if (s == "--collate") {
+            collate = true;
+        } else if (s == "--singletons") {
+            single_path = val("--singletons <FILE>");
+            has_single = true;
+        } else if (s == "--collate-memory") {
+            collate_memory = size_value(val("--collate-memory <SIZE>"), "--collate-memory <SIZE>");
+            has_memory = true;
         } else if (s == "--exclude-flags") {
             opt.exclude_flags = (uint32_t)int_value(val("--exclude-flags <INT>"), "--exclude-flags <INT>", 65535);
         } else if (s == "--require-flags") {
@@ -157,31 +179,37 @@ int fastq_main(int argc, char **argv, int at) {
     if (pos.size() > 3) bail("unexpected argument '" + pos[3] + "' found");
     const bool two_files = pos.size() == 3;
     if (has_other && !two_files) bail("the argument '--other <FILE>' needs <READ_TWOS_FILE>: in one-file mode every read goes to the one file");
+    if (has_single && !collate) bail("the argument '--singletons <FILE>' needs --collate");
+    if (has_memory && !collate) bail("the argument '--collate-memory <SIZE>' needs --collate");
     // (0) the outputs' formats and names, then the input: every refusal comes before any file is created
-    Output o[3];
+    Output o[4];
     o[0].path = pos[1], o[0].opening = "opening reads one file: ", o[0].writing = "read one file";
     o[1].path = two_files ? pos[2] : "", o[1].opening = "opening reads two file: ", o[1].writing = "read two file";
     o[2].path = other_path, o[2].opening = "opening other reads file: ", o[2].writing = "other reads file";
-    const int n_out = !two_files ? 1 : has_other ? 3 : 2;
-    for (int k = 0; k < n_out; k++) {
+    o[3].path = single_path, o[3].opening = "opening singletons file: ", o[3].writing = "singletons file";
+    std::vector<int> act = {0}; // the outputs that are given, in the order of their numbers
+    if (two_files) act.push_back(1);
+    if (two_files && has_other) act.push_back(2);
+    if (has_single) act.push_back(3);
+    for (const int k : act) {
         const std::string e = check_output(&o[k]);
         if (!e.empty()) bail(o[k].opening + o[k].path + ": " + e);
     }
-    for (int k = 0; k < n_out; k++)
-        for (int j = 0; j < k; j++)
-            if (same_file(o[j].path, o[k].path)) bail(o[k].opening + o[k].path + ": the same file as the " + o[j].writing);
+    for (const int k : act)
+        for (const int j : act)
+            if (j < k && same_file(o[j].path, o[k].path)) bail(o[k].opening + o[k].path + ": the same file as the " + o[j].writing);
     bool any_gzip = false;
-    for (int k = 0; k < n_out; k++) any_gzip |= o[k].gzip;
+    for (const int k : act) any_gzip |= o[k].gzip;
     if (has_effort && !(gzip_device && any_gzip)) bail("--gzip-effort needs --gzip device");
     const std::string &src = pos[0];
     const std::string format = detect_format(src);
     if (format.empty()) bail("failed to detect from input filetype: " + src + ": Failed parsing of bioinformatics file format.");
     if (format != "BAM") bail("opening BAM input file: " + src + ": incompatible formats: required BAM, found " + format);
-    for (int k = 0; k < n_out; k++)
+    for (const int k : act)
         if (same_file(src, o[k].path)) bail(o[k].opening + o[k].path + ": the same file as the input");
     ngsq_bam *bam = nullptr;
     if (ngsq_bam_open(src.c_str(), 0, &bam) != NGSQ_OK) bail(std::string("opening BAM input file: ") + ngsq_bam_last_error());
-    for (int k = 0; k < n_out; k++) // (a link to the input made under another name)
+    for (const int k : act) // (a link to the input made under another name)
         if (same_file(src, o[k].path)) bail(o[k].opening + o[k].path + ": the same file as the input");
     logf(2, "Starting fastq command...");
     // (1) the device, then the outputs, read ones first: a machine without a device leaves no file behind
@@ -190,7 +218,7 @@ int fastq_main(int argc, char **argv, int at) {
         ngsq_bam_close(bam);
         bail(ngsq_last_global_error());
     }
-    for (int k = 0; k < n_out; k++) {
+    for (const int k : act) {
         o[k].fd = open(o[k].path.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
         if (o[k].fd < 0) {
             const int e = errno;
@@ -204,28 +232,39 @@ int fastq_main(int argc, char **argv, int at) {
     const bool on_device = gzip_device && any_gzip;
     std::string msg;
     if (ngsq_bgzf_set_effort(ctx, effort) != NGSQ_OK) msg = ngsq_last_error(ctx);
-    for (int k = 0; k < n_out && msg.empty(); k++) {
+    for (const int k : act) {
+        if (!msg.empty()) break;
         if (!o[k].gzip) continue;
         if (on_device) opt.bgzf_mask |= 1u << k;
         else if (ngsq_gzip_pipe_open(o[k].fd, 8, &o[k].gz, &o[k].write_fd) != NGSQ_OK) msg = std::string(o[k].opening) + o[k].path + ": could not start the compressor";
     }
     ngsq_fastq_report rep{};
+    ngsq_collate_report crep{};
     if (msg.empty() && has_n && n == 0) {
         // no record is examined: every output is empty, which for a BGZF output is the EOF block alone
-        for (int k = 0; k < n_out && msg.empty(); k++)
-            if (opt.bgzf_mask >> k & 1) {
+        for (const int k : act)
+            if (msg.empty() && (opt.bgzf_mask >> k & 1)) {
                 uint8_t eof[64];
                 uint64_t len = 0;
                 if (ngsq_bgzf_deflate_device(ctx, nullptr, 0, eof, sizeof eof, &len, NGSQ_BGZF_EOF, nullptr) != NGSQ_OK) msg = ngsq_last_error(ctx);
                 else if (write(o[k].fd, eof, (size_t)len) != (ssize_t)len)
                     msg = std::string("could not write record to ") + o[k].writing + ": " + strerror(errno) + " (os error " + std::to_string(errno) + ")";
             }
+    } else if (msg.empty() && collate) {
+        ngsq_collate_options copt{};
+        copt.struct_size = sizeof copt;
+        copt.require_flags = opt.require_flags, copt.exclude_flags = opt.exclude_flags;
+        copt.default_quality = opt.default_quality, copt.name_suffix = opt.name_suffix, copt.bgzf_mask = opt.bgzf_mask;
+        copt.max_records = has_n ? n : 0;
+        copt.memory_budget = collate_memory;
+        auto fd_of = [&](int k) { return std::find(act.begin(), act.end(), k) != act.end() ? o[k].write_fd : -1; };
+        if (ngsq_bam_write_fastq_collated(bam, ctx, fd_of(0), fd_of(1), fd_of(2), fd_of(3), &copt, &crep) != NGSQ_OK) msg = ngsq_bam_last_error();
     } else if (msg.empty()) {
         opt.max_records = has_n ? n : 0;
-        if (ngsq_bam_write_fastq(bam, ctx, o[0].write_fd, two_files ? o[1].write_fd : -1, n_out > 2 ? o[2].write_fd : -1, &opt, &rep) != NGSQ_OK)
+        if (ngsq_bam_write_fastq(bam, ctx, o[0].write_fd, two_files ? o[1].write_fd : -1, has_other ? o[2].write_fd : -1, &opt, &rep) != NGSQ_OK)
             msg = ngsq_bam_last_error();
     }
-    for (int k = 0; k < n_out; k++) {
+    for (const int k : act) {
         int e = 0;
         if (o[k].gz) {
             close(o[k].write_fd); // the pipe's end: the compressor finishes
@@ -237,6 +276,25 @@ int fastq_main(int argc, char **argv, int at) {
     if (ctx) ngsq_destroy(ctx);
     ngsq_bam_close(bam);
     if (!msg.empty()) bail(msg);
+    if (collate) {
+        logf(2, "%llu pairs, %llu singletons (%llu ambiguous, %llu dropped), %llu other reads dropped", (unsigned long long)crep.pairs,
+             (unsigned long long)crep.singletons, (unsigned long long)crep.ambiguous, (unsigned long long)crep.dropped_singletons,
+             (unsigned long long)crep.dropped_other);
+        if (g_level >= 3)
+            fprintf(stderr, "[ngs] fastq --collate: %llu records in %llu batches: %llu excluded, %llu without a sequence, %llu read ones, %llu read twos, "
+                            "%llu others; %llu resident records of %llu bytes, %llu sort passes, %llu name collisions, %llu pieces; "
+                            "%llu + %llu + %llu + %llu text bytes, %llu + %llu + %llu + %llu compressed; walk %.1f ms (ingest %.1f ms), match %.1f ms, format %.1f ms, "
+                            "deflate %.1f ms, copy %.1f ms, write %.1f ms, total %.1f ms\n",
+                    (unsigned long long)crep.records_scanned, (unsigned long long)crep.batches, (unsigned long long)crep.excluded,
+                    (unsigned long long)crep.no_sequence, (unsigned long long)crep.reads_one, (unsigned long long)crep.reads_two,
+                    (unsigned long long)crep.reads_other, (unsigned long long)crep.resident_records, (unsigned long long)crep.resident_bytes,
+                    (unsigned long long)crep.sort_passes, (unsigned long long)crep.name_collisions, (unsigned long long)crep.pieces,
+                    (unsigned long long)crep.text_bytes[0], (unsigned long long)crep.text_bytes[1], (unsigned long long)crep.text_bytes[2],
+                    (unsigned long long)crep.text_bytes[3], (unsigned long long)crep.compressed_bytes[0], (unsigned long long)crep.compressed_bytes[1],
+                    (unsigned long long)crep.compressed_bytes[2], (unsigned long long)crep.compressed_bytes[3], crep.walk_ms, crep.scan_ms, crep.match_ms,
+                    crep.format_ms, crep.deflate_ms, crep.copy_ms, crep.write_ms, crep.total_ms);
+        return 0;
+    }
     if (two_files && rep.reads_one != rep.reads_two)
         logf(2, "%llu read ones and %llu read twos were written: the two files do not pair line by line", (unsigned long long)rep.reads_one,
              (unsigned long long)rep.reads_two);

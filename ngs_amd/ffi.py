@@ -255,6 +255,30 @@ class FastqReport(C.Structure):
                 ("copy_ms", C.c_double), ("write_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+# ---- include/ngsq_collate.h -------------------------------------------------------------------
+FASTQ_SINGLE = 3
+COLLATE_MAX_RUN = 1024
+
+
+class CollateOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("require_flags", C.c_uint32), ("exclude_flags", C.c_uint32),
+                ("default_quality", C.c_uint32), ("name_suffix", C.c_uint32), ("bgzf_mask", C.c_uint32),
+                ("hash_bits", C.c_uint32), ("reserved", C.c_uint32), ("max_records", C.c_uint64), ("batch_records", C.c_uint64),
+                ("piece_records", C.c_uint64), ("memory_budget", C.c_uint64)]
+
+
+class CollateReport(C.Structure):
+    _fields_ = [("records_scanned", C.c_uint64), ("excluded", C.c_uint64), ("no_sequence", C.c_uint64), ("reads_one", C.c_uint64),
+                ("reads_two", C.c_uint64), ("reads_other", C.c_uint64), ("dropped_other", C.c_uint64), ("pairs", C.c_uint64),
+                ("singletons", C.c_uint64), ("ambiguous", C.c_uint64), ("dropped_singletons", C.c_uint64),
+                ("name_collisions", C.c_uint64), ("batches", C.c_uint64), ("resident_records", C.c_uint64),
+                ("resident_bytes", C.c_uint64), ("sort_passes", C.c_uint64), ("pieces", C.c_uint64),
+                ("text_bytes", C.c_uint64 * 4), ("compressed_bytes", C.c_uint64 * 4), ("blocks", C.c_uint64),
+                ("stored_blocks", C.c_uint64), ("scan_ms", C.c_double), ("walk_ms", C.c_double), ("match_ms", C.c_double),
+                ("format_ms", C.c_double), ("deflate_ms", C.c_double), ("copy_ms", C.c_double), ("write_ms", C.c_double),
+                ("total_ms", C.c_double)]
+
+
 # ---- include/ngsq_samtext.h -------------------------------------------------------------------
 class SamTextReport(C.Structure):
     _fields_ = [("records", C.c_uint64), ("header_bytes", C.c_uint64), ("text_bytes", C.c_uint64), ("bam_bytes", C.c_uint64),
@@ -535,6 +559,9 @@ PROTOTYPES = {
     "ngsq_bam_write_sam": (C.c_int, [C.c_void_p, ctx_p, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(SamReport)]),
     # include/ngsq_fastq.h
     "ngsq_bam_write_fastq": (C.c_int, [C.c_void_p, ctx_p, C.c_int, C.c_int, C.c_int, C.POINTER(FastqOptions), C.POINTER(FastqReport)]),
+    # include/ngsq_collate.h
+    "ngsq_collate_bytes_per_record": (C.c_uint64, []),
+    "ngsq_bam_write_fastq_collated": (C.c_int, [C.c_void_p, ctx_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CollateOptions), C.POINTER(CollateReport)]),
     # include/ngsq_samtext.h
     "ngsq_sam_check_header": (C.c_int, [C.c_char_p, u32p, C.c_char_p, C.c_size_t]),
     "ngsq_sam_write_bam": (C.c_int, [ctx_p, C.c_char_p, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(SamTextReport)]),

@@ -591,6 +591,39 @@ def bam_to_fastq(path: str, path_one: str, path_two: Optional[str] = None, path_
                     os.close(fd)
 
 
+def bam_to_fastq_collated(path: str, path_one: str, path_two: Optional[str] = None, path_other: Optional[str] = None,
+                          path_single: Optional[str] = None, device: int = 0, exclude_flags: int = ffi.FASTQ_EXCLUDE_FLAGS,
+                          require_flags: int = 0, name_suffix: bool = False, default_quality: int = ffi.FASTQ_DEFAULT_QUALITY,
+                          bgzf_mask: int = 0, hash_bits: int = 0, max_records: int = 0, batch_records: int = 0, piece_records: int = 0,
+                          memory_budget: int = 0, effort: str = "normal", lib=None) -> Dict[str, object]:
+    """`ngs fastq --collate` in process (include/ngsq_collate.h): the reads of the BAM `path` as FASTQ with the mates paired by
+    name, whatever the order of the file.  With path_two, pair p's read one is record p of path_one and its read two record p of
+    path_two; without it path_one is interleaved.  Singletons go to path_single and others to path_other (with path_two only),
+    or are dropped and counted.  bgzf_mask: bit 0 / 1 / 2 / 3: that output is BGZF from the device encoder at `effort`.
+    hash_bits, batch_records, piece_records and memory_budget change how the work is cut, never what is written (0: the
+    library's defaults).  Returns the report, its four-entry arrays as lists; NgsqError on an open failure, a refused argument,
+    a kept record with a quality score above 93, records beyond the budget or a run of names beyond the run limit."""
+    lib = lib or ffi.load_library()
+    with _reader_and_plain_context(lib, path, device, "opening BAM input file: ") as (bam, ctx):
+        _set_effort(lib, ctx, effort)
+        fds = []
+        try:
+            for p in (path_one, path_two, path_other, path_single):
+                fds.append(-1 if p is None else os.open(p, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o666))
+            opt = ffi.CollateOptions()
+            opt.struct_size = C.sizeof(ffi.CollateOptions)
+            opt.require_flags, opt.exclude_flags, opt.default_quality = require_flags, exclude_flags, default_quality
+            opt.name_suffix, opt.bgzf_mask, opt.hash_bits = int(name_suffix), bgzf_mask, hash_bits
+            opt.max_records, opt.batch_records, opt.piece_records, opt.memory_budget = max_records, batch_records, piece_records, memory_budget
+            rep = ffi.CollateReport()
+            _check_bam(lib.ngsq_bam_write_fastq_collated(bam, ctx, fds[0], fds[1], fds[2], fds[3], C.byref(opt), C.byref(rep)), lib)
+            return {k: (list(getattr(rep, k)) if k in ("text_bytes", "compressed_bytes") else getattr(rep, k)) for k, _ in ffi.CollateReport._fields_}
+        finally:
+            for fd in fds:
+                if fd >= 0:
+                    os.close(fd)
+
+
 BGZF_EFFORTS = {"normal": ffi.BGZF_EFFORT_NORMAL, "high": ffi.BGZF_EFFORT_HIGH}
 
 
