@@ -134,25 +134,46 @@ __global__ __launch_bounds__(CS_THREADS) void k_cov_scan(CovScanArgs a) {
 #pragma unroll
         for (uint32_t r = 0; r < CS_PER_THREAD / 4; r++) v[r] = src[r];
     };
+    // what next_live() asks of the current sequence, loaded where `ref` changes and not per chunk: its first chunk
+    // behind it and whether it has an entry (coverage.rs:187-193: only sequences with one are torn down)
+    uint64_t ref_c1 = a.ref_first_chunk[ref + 1];
+    bool ref_seen = a.seen[ref] != 0;
     // first chunk >= c this wave really has to read (skips sequences without an entry)
     auto next_live = [&](uint64_t c) -> uint64_t {
         while (c < c_hi) {
-            while (ref + 1 < a.n_refs && c >= a.ref_first_chunk[ref + 1]) {
+            while (ref + 1 < a.n_refs && c >= ref_c1) {
                 if (dirty) flush_hist(ref);
                 dirty = false;
                 ref += 1;
+                ref_c1 = a.ref_first_chunk[ref + 1];
+                ref_seen = a.seen[ref] != 0;
             }
-            if (a.seen[ref] != 0) { // coverage.rs:187-193: only sequences with an entry
-                if (SKIP && a.chunk_flags[c]) {
-                    carry += a.chunk_sums[c];
-                    c += 1;
-                    continue;
+            if (ref_seen) {
+                if (SKIP) {
+                    // 64 chunks at a time: lane i looks at chunk c + i, as far as the wave's range and the sequence go.
+                    // The flagged chunks in front of the first one that is not flagged are passed together: their sums
+                    // join the carry (modulo 2^32, like the running sum itself).  A lane past the limit counts as not
+                    // flagged, so the group ends there and the loop's head deals with the limit.
+                    const uint64_t lim = ref + 1 < a.n_refs && ref_c1 < c_hi ? ref_c1 : c_hi; // c < lim
+                    const uint64_t ci = c + lane;
+                    const bool in = ci < lim;
+                    const bool flagged = in && a.chunk_flags[ci] != 0;
+                    uint32_t sum = in ? a.chunk_sums[ci] : 0u;
+                    const u64 open = ~__ballot(flagged); // wave-uniform control flow: all 64 lanes are here
+                    const uint32_t n = open ? (uint32_t)__ffsll((long long)open) - 1u : 64u;
+                    if (n) {
+                        sum = lane < n ? sum : 0u;
+#pragma unroll
+                        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+                        carry += sum;
+                        c += n;
+                        if (n == 64 || c >= lim) continue; // nothing live met yet
+                    }
                 }
                 load_ref(ref);
                 return c;
             }
-            const uint64_t ref_end = a.ref_first_chunk[ref + 1];
-            c = ref_end < c_hi ? ref_end : c_hi;
+            c = ref_c1 < c_hi ? ref_c1 : c_hi;
         }
         return c_hi;
     };

@@ -479,6 +479,7 @@ static uint32_t qp_period(uint32_t pitch) {
     return pitch / (low < 16u ? low : 16u);
 }
 constexpr uint32_t QP_THREADS = 1024;
+typedef uint32_t qp_u32x4 __attribute__((ext_vector_type(4)));
 
 // exact tally of bytes [j_lo, j_hi) of one window (rare: a 0xFF cell, a score >= 64 or an invalid byte in it, or
 // a window at an end of the buffer); c0 = cycle of byte 0 of the window
@@ -602,7 +603,11 @@ __global__ __launch_bounds__(1024) void k_qual_perm(DeviceState st, const uint8_
         }
     };
     auto load = [&]() -> uint4 {
-        const uint4 v = *pf; // one aligned global_load_dwordx4
+        // one aligned global_load_dwordx4, non-temporal: every line of the stream is read by this one wave instruction, once, so
+        // keeping it in a cache buys nothing (2.57 -> 2.32 ms per launch on 100 M x 150 bp, profiles/r25_step_gaps.txt; on windows
+        // of a row, where lanes and waves shared lines, the policy had changed nothing)
+        const qp_u32x4 x = __builtin_nontemporal_load(reinterpret_cast<const qp_u32x4 *>(pf));
+        const uint4 v = make_uint4(x.x, x.y, x.z, x.w);
         pf += stride;
         return v;
     };
