@@ -21,7 +21,8 @@ SOURCES = ["kernels.hip", "qual_kernel.hip", "fields_kernel.hip", "cov_scan.hip"
            "samtext_kernel.hip", "samtext.cpp",
            "sort_kernel.hip", "sort.cpp", "samsort.cpp", "samsort_header.cpp", "bamsort.cpp",
            "depth_kernel.hip", "depth.cpp", "depth_bed.cpp", "depth_windows_kernel.hip", "depth_windows.cpp",
-           "fastq_kernel.hip", "fastq.cpp", "collate_kernel.hip", "collate.cpp"]
+           "fastq_kernel.hip", "fastq.cpp", "collate_kernel.hip", "collate.cpp",
+           "markdup_kernel.hip", "markdup.cpp"]
 HEADERS = ["kernels.h", "context.h", "comm.h", "mem_pool.h", "bam_reader.h", "ingest_consumer.h", "ingest_kernels.h", "bgzf.h", "bgzf_crc.h", "deflate_kernels.h", "../../include/ngsq_bgzf.h", "reference_kernels.h", "../../include/ngsq.h",
            "../../include/ngsq_reference.h", "../../include/ngsq_comm.h",
            "../../include/ngsq_shared.h", "../../include/ngsq_synth.h", "../../include/ngsq_bam.h", "../../include/ngsq_stage.h",
@@ -32,7 +33,8 @@ HEADERS = ["kernels.h", "context.h", "comm.h", "mem_pool.h", "bam_reader.h", "in
            "samtext_kernels.h", "samtext_host.h", "samtext_run.h", "../../include/ngsq_samtext.h",
            "sort_kernels.h", "../../include/ngsq_sort.h", "sort_resident.h", "../../include/ngsq_bamsort.h",
            "depth_kernels.h", "depth_run.h", "depth_windows_kernels.h", "../../include/ngsq_depth.h",
-           "fastq_kernels.h", "fastq_format.h", "../../include/ngsq_fastq.h", "collate_kernels.h", "../../include/ngsq_collate.h"]
+           "fastq_kernels.h", "fastq_format.h", "../../include/ngsq_fastq.h", "collate_kernels.h", "../../include/ngsq_collate.h",
+           "name_key.h", "markdup_kernels.h", "../../include/ngsq_markdup.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-result", "-fno-gpu-rdc"]
 FLAGS += os.environ.get("NGSQ_EXTRA_FLAGS", "").split()  # extra compiler flags for a local build, e.g. -save-temps (use --force)
 OBJ_DIR = os.path.join(HERE, "_obj")  # per-source objects (git-ignored): only changed sources recompile
@@ -54,10 +56,10 @@ def up_to_date() -> bool:
 
 
 CLI_DIR = os.path.join(CSRC, "cli")
-CLI_SOURCES = [os.path.join(CLI_DIR, f) for f in ("ngs_main.cpp", "qc.cpp", "index.cpp", "convert.cpp", "derive.cpp", "view.cpp", "generate.cpp", "depth.cpp", "fastq.cpp")]  # one file per command
+CLI_SOURCES = [os.path.join(CLI_DIR, f) for f in ("ngs_main.cpp", "qc.cpp", "index.cpp", "convert.cpp", "derive.cpp", "view.cpp", "generate.cpp", "depth.cpp", "fastq.cpp", "markdup.cpp")]  # one file per command
 CLI_HEADERS = sorted(os.path.join(CLI_DIR, f) for f in os.listdir(CLI_DIR) if f.endswith(".h"))
 CLI_PUBLIC_HEADERS = [os.path.join(HERE, "..", "include", f) for f in (
-    "ngsq.h", "ngsq_bam.h", "ngsq_bamsort.h", "ngsq_bgzf.h", "ngsq_collate.h", "ngsq_comm.h", "ngsq_depth.h", "ngsq_derive.h", "ngsq_fastq.h", "ngsq_generate.h", "ngsq_index.h", "ngsq_reference.h", "ngsq_sam.h", "ngsq_samtext.h", "ngsq_sort.h", "ngsq_stage.h", "ngsq_view.h")]
+    "ngsq.h", "ngsq_bam.h", "ngsq_bamsort.h", "ngsq_bgzf.h", "ngsq_collate.h", "ngsq_comm.h", "ngsq_depth.h", "ngsq_derive.h", "ngsq_fastq.h", "ngsq_generate.h", "ngsq_index.h", "ngsq_markdup.h", "ngsq_reference.h", "ngsq_sam.h", "ngsq_samtext.h", "ngsq_sort.h", "ngsq_stage.h", "ngsq_view.h")]
 CLI_OUT = os.path.join(HERE, "ngs")
 
 

@@ -1,6 +1,6 @@
 // cli.h -- what the commands of `ngs` share: the log, the error exit, option helpers, file-format sniffing, and the
-// reader plus facet-less context that `index`, `convert`, `derive`, `view`, `depth` and `fastq` walk a file with.  One file per command beside it:
-// qc.cpp, index.cpp, convert.cpp, derive.cpp, view.cpp, generate.cpp, depth.cpp, fastq.cpp; ngs_main.cpp dispatches.  The command line includes the library's public headers only.
+// reader plus facet-less context that `index`, `convert`, `derive`, `view`, `depth`, `fastq` and `markdup` walk a file with.  One file per command beside it:
+// qc.cpp, index.cpp, convert.cpp, derive.cpp, view.cpp, generate.cpp, depth.cpp, fastq.cpp, markdup.cpp; ngs_main.cpp dispatches.  The command line includes the library's public headers only.
 #pragma once
 
 #include <unistd.h>
@@ -29,6 +29,7 @@ int view_main(int argc, char **argv, int at);
 int generate_main(int argc, char **argv, int at);
 int depth_main(int argc, char **argv, int at);
 int fastq_main(int argc, char **argv, int at);
+int markdup_main(int argc, char **argv, int at);
 
 inline int g_level = 2; // 0 off (-q), 2 info (default), 3 debug (-v)   src/main.rs:71-83
 

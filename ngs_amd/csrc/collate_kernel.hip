@@ -8,6 +8,7 @@
 
 #include "collate_kernels.h"
 #include "fastq_format.h"
+#include "name_key.h"
 
 namespace ngsq {
 
@@ -17,9 +18,7 @@ constexpr uint32_t BT = 256;
 constexpr uint32_t WAVES = BT / 64;
 
 __device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
-__device__ __forceinline__ const uint8_t *body_at(const uint64_t *addr, uint64_t i) { return reinterpret_cast<const uint8_t *>((uintptr_t)addr[i]) + 4; }
 __device__ __forceinline__ uint32_t class_of(uint32_t flag) { return (flag & 0xC0u) == 0x40u ? CLASS_ONE : (flag & 0xC0u) == 0x80u ? CLASS_TWO : CLASS_OTHER; }
-__device__ __forceinline__ uint32_t name_bytes(const uint8_t *body) { return body[8] ? body[8] - 1u : 0u; }
 
 __global__ __launch_bounds__(BT) void k_collate_flag(const uint8_t *__restrict__ raw, const uint64_t *__restrict__ rec_off, uint64_t n, FastqRules R,
                                                      uint64_t *__restrict__ cnt, uint64_t *__restrict__ bytes, unsigned long long *work) {
@@ -66,26 +65,6 @@ __global__ __launch_bounds__(BT) void k_collate_qual(const uint8_t *__restrict__
     if (__any(bad) && lane_id() == 0) (void)atomicMin(&work[CW_BAD], (unsigned long long)(first_index + r) << FASTQ_ERR_BITS | FASTQ_E_QUAL);
 }
 
-// a 64-bit hash of the name's bytes and their number: eight bytes a step, the rest by bytes; nothing behind the name is read
-__device__ __forceinline__ uint64_t name_hash(const uint8_t *name, uint32_t qn) {
-    constexpr uint64_t M = 0x9E3779B97F4A7C15ull;
-    uint64_t h = 0x243F6A8885A308D3ull ^ qn;
-    uint32_t k = 0;
-    for (; k + 8 <= qn; k += 8) {
-        uint64_t w;
-        __builtin_memcpy(&w, name + k, 8);
-        h = (h ^ w) * M;
-        h ^= h >> 29;
-    }
-    uint64_t w = 0;
-    for (uint32_t q = 0; k + q < qn; q++) w |= (uint64_t)name[k + q] << (8u * q);
-    h = (h ^ w) * M;
-    h ^= h >> 32;
-    h *= 0xD6E8FEB86659FD93ull;
-    h ^= h >> 32;
-    return h;
-}
-
 __global__ __launch_bounds__(BT) void k_collate_key(const uint64_t *__restrict__ addr, uint64_t n, uint64_t mask, uint64_t *__restrict__ key,
                                                     uint8_t *__restrict__ cls) {
     const uint64_t i = (uint64_t)blockIdx.x * BT + threadIdx.x;
@@ -101,12 +80,6 @@ __global__ __launch_bounds__(BT) void k_collate_run_limit(const uint64_t *__rest
     if (r + COLLATE_MAX_RUN >= n) return;
     const uint64_t k = skey[r];
     if (k != COLLATE_KEY_OTHER && k == skey[r + COLLATE_MAX_RUN]) work[CW_LONG_RUN] = 1ull;
-}
-
-__device__ __forceinline__ bool same_name(const uint8_t *a, const uint8_t *b, uint32_t qn) {
-    for (uint32_t k = 0; k < qn; k++)
-        if (a[k] != b[k]) return false;
-    return true;
 }
 
 __global__ __launch_bounds__(BT) void k_collate_match(const uint64_t *__restrict__ skey, const uint32_t *__restrict__ perm, const uint64_t *__restrict__ addr,

@@ -10,6 +10,8 @@
 // positions behind the last piece; bai.cpp's writer makes the file once the EOF block is out.
 // Phases 2 and 3 come in steps -- the file's beginning, a round, the file's end -- so that bamsort.cpp can sort a BAM beyond the
 // budget in rounds: each round's records are resident in turn and continue the same stream of pieces.
+// `ngs markdup` (markdup.cpp) keeps its records and writes its pieces through this object too, in an order
+// of its own (order_given, write_records) instead of the sort's.
 #pragma once
 
 #include <cstdarg>
@@ -309,6 +311,20 @@ struct SortResident {
         }
         return ix.on ? index_tiles() : NGSQ_OK;
     }
+    // This order, no sort (`ngs markdup`): the m records order_[0, m) of the resident ones, in that order,
+    // are the stream's next bytes.  *bytes receives what they take; write_records(m, *bytes) writes them.
+    int order_given(const uint32_t *order_, uint64_t m, uint64_t *bytes) {
+        perm = order_;
+        *bytes = 0;
+        if (!m) return NGSQ_OK;
+        SRHIP(d_soff.reserve(m + 1));
+        SRHIP(launch_sort_lengths(d_len.p, perm, m, d_soff.p, st));
+        SRHIP(scan.exclusive_scan(d_soff.p, m + 1, st));
+        SRHIP(launch_samtext_word(d_soff.p, m, static_cast<unsigned long long *>(hw.dev), st));
+        SRHIP(hipStreamSynchronize(st));
+        *bytes = *static_cast<const unsigned long long *>(hw.h);
+        return NGSQ_OK;
+    }
     // the writer, and the header stream hs in front of a sorted stream of `stream_bytes` bytes cut into pieces of piece_bytes_
     int write_begin(int fd, const std::string &hs, uint64_t piece_bytes_, uint64_t stream_bytes) {
         piece_bytes = piece_bytes_;
@@ -329,8 +345,11 @@ struct SortResident {
     // The resident records to their places in the pieces.  Piece j is bytes [j * piece_bytes, (j + 1) * piece_bytes) of the file's
     // sorted stream, whatever round they come from: a piece this round leaves partly filled stays in d_piece, the next round's
     // gather continues behind it, and it is compressed when it is full or the stream ends.
-    int write_round() {
-        if (!records) return NGSQ_OK;
+    int write_round() { return write_records(records, rec_bytes); }
+    // write_round for an order of the caller's (order_given): the `n` records of perm, `bytes` bytes, are the stream's next
+    int write_records(uint64_t n, uint64_t bytes) {
+        if (!n) return NGSQ_OK;
+        const uint64_t records = n, rec_bytes = bytes; // (what the round writes, in the names the round's steps use)
         const uint64_t begin = stream_at, end = begin + rec_bytes;
         if (end > total) return fail(NGSQ_ERR_STATE, "the rounds' records take more than the %llu bytes of the sorted stream", (unsigned long long)total);
         const uint64_t j0 = begin / piece_bytes, j1 = (end + piece_bytes - 1) / piece_bytes;

@@ -279,6 +279,22 @@ class CollateReport(C.Structure):
                 ("total_ms", C.c_double)]
 
 
+# ---- include/ngsq_markdup.h -------------------------------------------------------------------
+class MarkdupOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("remove", C.c_uint32), ("hash_bits", C.c_uint32), ("reserved", C.c_uint32),
+                ("max_records", C.c_uint64), ("batch_records", C.c_uint64), ("piece_bytes", C.c_uint64), ("memory_budget", C.c_uint64)]
+
+
+MARKDUP_METRICS = ("records", "candidates", "pairs", "fragments", "duplicate_pairs", "duplicate_fragments", "duplicate_records", "cleared",
+                   "ambiguous", "name_collisions")
+
+
+class MarkdupReport(C.Structure):
+    _fields_ = ([(k, C.c_uint64) for k in MARKDUP_METRICS] + [("duplication", C.c_double)] +
+                [(k, C.c_uint64) for k in ("batches", "resident_bytes", "sort_passes", "pieces", "blocks", "stored_blocks", "bam_bytes", "compressed_bytes")] +
+                [(k + "_ms", C.c_double) for k in ("scan", "walk", "ends", "match", "mark", "gather", "deflate", "d2h", "write", "total")])
+
+
 # ---- include/ngsq_samtext.h -------------------------------------------------------------------
 class SamTextReport(C.Structure):
     _fields_ = [("records", C.c_uint64), ("header_bytes", C.c_uint64), ("text_bytes", C.c_uint64), ("bam_bytes", C.c_uint64),
@@ -562,6 +578,9 @@ PROTOTYPES = {
     # include/ngsq_collate.h
     "ngsq_collate_bytes_per_record": (C.c_uint64, []),
     "ngsq_bam_write_fastq_collated": (C.c_int, [C.c_void_p, ctx_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CollateOptions), C.POINTER(CollateReport)]),
+    # include/ngsq_markdup.h
+    "ngsq_markdup_bytes_per_record": (C.c_uint64, []),
+    "ngsq_bam_mark_duplicates": (C.c_int, [C.c_void_p, ctx_p, C.c_int, C.POINTER(MarkdupOptions), C.POINTER(MarkdupReport)]),
     # include/ngsq_samtext.h
     "ngsq_sam_check_header": (C.c_int, [C.c_char_p, u32p, C.c_char_p, C.c_size_t]),
     "ngsq_sam_write_bam": (C.c_int, [ctx_p, C.c_char_p, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(SamTextReport)]),

@@ -624,6 +624,29 @@ def bam_to_fastq_collated(path: str, path_one: str, path_two: Optional[str] = No
                     os.close(fd)
 
 
+def bam_mark_duplicates(path: str, out_path: str, remove: bool = False, device: int = 0, hash_bits: int = 0, max_records: int = 0,
+                        batch_records: int = 0, piece_bytes: int = 0, memory_budget: int = 0, effort: str = "normal", lib=None) -> Dict[str, object]:
+    """`ngs markdup` in process (include/ngsq_markdup.h): the records of the BAM `path` written to out_path as BAM with flag 0x400
+    set on the duplicates and cleared on every other record, or with `remove` the duplicates left out.  hash_bits, batch_records,
+    piece_bytes, memory_budget and effort change how the work is cut and compressed, never the decompressed bytes (0: the
+    library's defaults).  out_path is created or truncated.  Returns the report; NgsqError on an open failure, a refused
+    argument, an unclipped end that cannot be packed, records beyond the budget or a run of names beyond the run limit."""
+    lib = lib or ffi.load_library()
+    with _reader_and_plain_context(lib, path, device, "opening BAM input file: ") as (bam, ctx):
+        _set_effort(lib, ctx, effort)
+        fd = os.open(out_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o666)
+        try:
+            opt = ffi.MarkdupOptions()
+            opt.struct_size = C.sizeof(ffi.MarkdupOptions)
+            opt.remove, opt.hash_bits, opt.max_records = int(remove), hash_bits, max_records
+            opt.batch_records, opt.piece_bytes, opt.memory_budget = batch_records, piece_bytes, memory_budget
+            rep = ffi.MarkdupReport()
+            _check_bam(lib.ngsq_bam_mark_duplicates(bam, ctx, fd, C.byref(opt), C.byref(rep)), lib)
+            return {k: getattr(rep, k) for k, _ in ffi.MarkdupReport._fields_}
+        finally:
+            os.close(fd)
+
+
 BGZF_EFFORTS = {"normal": ffi.BGZF_EFFORT_NORMAL, "high": ffi.BGZF_EFFORT_HIGH}
 
 
